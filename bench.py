@@ -7,7 +7,15 @@ Metric (BASELINE.json): attn fwd TFLOPS + %MFMA peak at (B,H,S,D) = (4,32,4096,1
 synthetic N(0,1) q, k, v already resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c5_layer|decode|window|...]
-                  [--weak] [--world W --rank R]
+                  [--weak] [--world W --rank R] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set-up, device warm-up, the W warm-up steps, the
+K timed steps, and the result line. ``--full`` adds the measurements that take runs of their own: the
+CPU baseline, the per-launch median of the roofline, and (c5_layer) the bare op and the unpatched HF
+layer timed beside the patched one. ``--dump-outputs DIR`` writes what the last timed step returned as
+``DIR/<name>.npy`` (float32; at most 64 MB in all, a fixed seeded sample of the rows of a larger output,
+the sampled row numbers beside it); the inputs depend only on ``--seed`` and the configuration, so two
+builds can be compared output for output.
 
 Multi-GPU (launched by torch.distributed.run, one process per GPU; attention tiles are independent,
 so there is no data-path collective -- SURVEY.md 8(e)). A gloo process group carries only the
@@ -30,8 +38,10 @@ Rank 0 prints ONE JSON line. Besides the contract fields it carries
                  timed region's back-to-back launches, per launch) against the dense fp16 MFMA
                  peak; ``traffic`` is
                  the HBM bytes per launch from the committed rocprofv3 PMC pass (profiles/), or null;
-  cpu_baseline : torch SDPA fp32 on the host cores (the reference op's CPU path, BASELINE.md's CPU
-                 baseline) on the same workload; ``port`` = oracle/fa_oracle.c on a bounded sample.
+                 with ``--full`` also the median over single launches (``kernel_ms_median``);
+  cpu_baseline : (``--full``, else null) torch SDPA fp32 on the host cores (the reference op's CPU
+                 path, BASELINE.md's CPU baseline) on the same workload; ``port`` = oracle/fa_oracle.c
+                 on a bounded sample.
 """
 from __future__ import annotations
 
@@ -447,6 +457,37 @@ def layer_setup(c, dev, dt, seed):
     return patched_call, info
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(outputs, out_dir, suffix: str = "") -> dict:
+    """Write what a step returned (a tensor or a list of tensors) as float32 ``<name>.npy`` files under
+    ``out_dir``: ``out`` for one tensor, ``out_<i>`` for the i-th of several. An output larger than its
+    share of DUMP_BYTES is written as a sample of its rows (the last dimension kept whole): the rows are
+    drawn once from a fixed seed and the output's shape only, so every run and build draws the same."""
+    import numpy as np
+    import torch
+
+    outs = [outputs] if isinstance(outputs, torch.Tensor) else list(outputs)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(outs)) // 4  # float32 elements per file
+    written = {}
+    for i, t in enumerate(outs):
+        name = ("out" if len(outs) == 1 else f"out_{i}") + suffix
+        rows = t.reshape(-1, t.shape[-1])
+        keep = max(1, budget // rows.shape[1])
+        if rows.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(1234).choice(rows.shape[0], size=keep, replace=False))
+            rows = rows[torch.from_numpy(idx).to(rows.device)]
+            written[name] = {"shape": list(t.shape), "rows_sampled": int(keep), "of": int(t.numel() // t.shape[-1])}
+        else:
+            rows = t
+            written[name] = {"shape": list(t.shape)}
+        np.save(d / f"{name}.npy", rows.detach().float().cpu().numpy())
+    return written
+
+
 def reduce_max(world: int, *vals: float):
     """Max over ranks of host-side timings (gloo, CPU tensor): the harness's only cross-rank traffic."""
     if world <= 1:
@@ -466,7 +507,11 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="CPU port sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: CPU baseline, per-launch median, c5_layer's side timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--strong", action="store_true", help="(the default) split one global problem over the ranks")
     ap.add_argument("--weak", action="store_true", help="every rank runs the whole configured workload instead")
@@ -480,6 +525,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.strong and args.weak:
         ap.error("--strong and --weak exclude each other")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not started by torch.distributed.run: start it as a child (never exec) and pass its status on
@@ -567,6 +614,8 @@ def main() -> None:
         layer_step, layer_info = layer_setup(c, dev, dt, args.seed + rank)
         extra["layer"] = layer_info
 
+    last_out = []  # what the last call of the latest timed() returned (--dump-outputs)
+
     def timed(fn, n):
         """n back-to-back calls of fn between synchronisations: (wall s, HIP-event ms per call).
 
@@ -578,8 +627,9 @@ def main() -> None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         a.record()
-        for _ in range(n):
+        for _ in range(n - 1):
             fn()
+        last_out[:] = [fn()]  # (the n-th call; the others' results are dropped as they return)
         b.record()
         torch.cuda.synchronize()
         return time.perf_counter() - t0, a.elapsed_time(b) / n
@@ -609,12 +659,14 @@ def main() -> None:
         main_step()
     torch.cuda.synchronize()
 
-    if layer:  # the bare op and unpatched HF at the same dims, timed beside the patched layer
-        for key, fn in (("bare_op_ms", step), ("hf_sdpa_layer_ms", layer_info.pop("_hf_step")),
-                        ("unfused_rope_layer_ms", layer_info.pop("_unfused_step"))):
+    if layer:  # --full: the bare op and unpatched HF at the same dims, timed beside the patched layer
+        side = (("bare_op_ms", step), ("hf_sdpa_layer_ms", layer_info.pop("_hf_step")),
+                ("unfused_rope_layer_ms", layer_info.pop("_unfused_step")))
+        for key, fn in side if args.full else ():
             timed(fn, 10)  # warm-up (library heuristics, first-call setup)
             extra["layer"][key] = round(timed(fn, max(args.steps, 10))[1], 4)
-        for _ in range(args.warmup):
+            last_out.clear()
+        for _ in range(args.warmup if args.full else 0):
             main_step()
 
     if world > 1:
@@ -623,11 +675,15 @@ def main() -> None:
     elapsed, step_ms = timed(main_step, args.steps)
     if world > 1:
         dist.barrier()
+    if args.dump_outputs:  # what the last timed step returned
+        extra["outputs"] = dump_outputs(last_out[0], args.dump_outputs, suffix=f"_rank{rank}" if rank else "")
+    last_out.clear()
     # the attention kernel alone (roofline): HIP events around the op's launches on the current stream
-    kern_ms = step_ms if not layer else extra["layer"]["bare_op_ms"]
-    # BASELINE.md's statistic beside the mean: the median over >= 50 launches, each between its own
-    # event pair (after the timed region, so the pairs' gaps do not touch `value`)
-    kern_med_ms, n_med = per_launch_median(step, max(50, args.steps))
+    # (the layer's bare op is timed only with --full)
+    kern_ms = step_ms if not layer else extra["layer"].get("bare_op_ms")
+    # BASELINE.md's statistic beside the mean (--full): the median over >= 50 launches, each between its
+    # own event pair (after the timed region, so the pairs' gaps do not touch `value`)
+    median = per_launch_median(step, max(50, args.steps)) if args.full else None
 
     (elapsed,) = reduce_max(world, elapsed)
 
@@ -635,7 +691,8 @@ def main() -> None:
         tokens = n_gpus * c["B"] * c["Sq"] * args.steps
         value, unit = tokens / elapsed, "tokens/s"
         extra["layer"]["layer_ms"] = round(elapsed * 1e3 / args.steps, 4)
-        extra["layer"]["hf_sdpa_tokens_per_s"] = round(c["B"] * c["Sq"] / (extra["layer"]["hf_sdpa_layer_ms"] * 1e-3), 1)
+        if args.full:
+            extra["layer"]["hf_sdpa_tokens_per_s"] = round(c["B"] * c["Sq"] / (extra["layer"]["hf_sdpa_layer_ms"] * 1e-3), 1)
         extra["layer"]["layer_TFLOPS"] = round((extra["layer"]["projection_flops"] + extra["layer"]["attention_flops"])
                                                / (elapsed / args.steps) / 1e12, 2)
     elif mode["emulated"]:  # the one GPU's share, timed alone
@@ -672,14 +729,16 @@ def main() -> None:
         "pct_mfma_peak": None if layer else round(100.0 * tf_per_gpu / PEAK_TFLOPS, 2),
         # rank 0's kernel: its FLOPs / bytes over the mean HIP-event time of its launches; the PMC
         # traffic only when these launches are the profiled (default N = 1) workload
-        "roofline": roofline(c, kern_ms, load_traffic(args.config) if mode["whole_default_workload"] else
+        "roofline": None if kern_ms is None else
+                    roofline(c, kern_ms, load_traffic(args.config) if mode["whole_default_workload"] else
                              (None, {"traffic_source": None, "traffic_note": "launches differ from the profiled "
                                      "workload (a shard or another batch)"}),
-                             rank_flops=rank_flops, rank_bytes=rank_bytes, median=(kern_med_ms, n_med)),
+                             rank_flops=rank_flops, rank_bytes=rank_bytes, median=median),
         "cpu_baseline": None,
+        "full": args.full,
         **extra,
     }
-    if rank == 0 and n_gpus == 1 and not mode["emulated"] and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not mode["emulated"] and not args.no_cpu_baseline:
         result["cpu_baseline"] = (cpu_layer_baseline(c, args.seed) if layer else
                                   cpu_baseline(q, k, v, c, args.cpu_seconds))
     if rank == 0:

@@ -77,14 +77,25 @@ def _jobs() -> int:
     return max(1, min(int(n), 16))
 
 
-def _process_pool():
-    """Worker processes for the assembly gate (a pure-Python dataflow over each instantiation, seconds each).
-    Spawned, not forked: a fork taken while the compile threads' pool still holds locks left the workers
-    hung (seen twice in round 6)."""
-    import multiprocessing
-    from concurrent.futures import ProcessPoolExecutor
+# (_asm_check.py is loaded by path: importing the package would import torch and, in a tree that is
+# not built yet, start a build of its own inside every child)
+_CHECK_CHILD = ("import json, runpy, sys; check_file = runpy.run_path(sys.argv[1])['check_file']; "
+                "print(json.dumps(check_file(sys.argv[2])))")
 
-    return ProcessPoolExecutor(max_workers=_jobs(), mp_context=multiprocessing.get_context("spawn"))
+
+def _check_asm(path) -> list[str]:
+    """The assembly gate (_asm_check.check_file, a pure-Python dataflow, seconds per instantiation) on one
+    file in a fresh interpreter, so the files are checked in parallel from plain threads. Not a
+    multiprocessing pool: forked workers hung on locks the compile threads' pool still held, and spawned
+    workers re-import the caller's main module, which fails when build() is called from a script read
+    from standard input (no file to import). A child that does not finish cleanly fails the build."""
+    import json
+
+    res = subprocess.run([sys.executable, "-c", _CHECK_CHILD, str(PKG / "_asm_check.py"), str(path)],
+                         capture_output=True, text=True)
+    if res.returncode != 0:
+        raise RuntimeError(f"assembly check of {path} did not run ({res.returncode}):\n{res.stdout}\n{res.stderr}")
+    return list(json.loads(res.stdout))
 
 
 def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, tag: str = "",
@@ -151,10 +162,8 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         for f in [ex.submit(compile_one, *c) for c in cmds]:
             f.result()
     # gate: the literal-AGPR invariant of fa_fwd_w4 and no VGPR spills (_asm_check)
-    from ._asm_check import check_file
-
-    with ThreadPoolExecutor(max_workers=1) if len(asm_files) < 2 else _process_pool() as ex:
-        problems = [p for ps in ex.map(check_file, asm_files) for p in ps]
+    with ThreadPoolExecutor(max_workers=_jobs()) as ex:
+        problems = [p for ps in ex.map(_check_asm, asm_files) for p in ps]
     if diag:  # stamp / experiment builds: spills are reported, not fatal (the AGPR rule stays)
         for q in [q for q in problems if "vgpr_spill_count" in q or not gate]:
             print(f"warning ({sdir}): {q}", flush=True)

@@ -4,7 +4,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; TAG=${1:-r2f}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd $R
 for c in c2 c3 c4 c5 window decode; do
-  timeout -k 10 200 python bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "bench $c failed"; exit 1; }
+  timeout -k 10 200 python bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "bench $c failed"; exit 1; }
 done
 export TMPDIR=/tmp; cd /tmp
 for c in c2 c4; do

@@ -8,7 +8,7 @@
 #   tests                  the whole `pytest -m gpu` suite
 #   tests=<expr>           the GPU tests matching `-k <expr>`
 #   smoke                  __graft_entry__.smoke()
-#   bench                  the driver's default `python bench.py` line (with the CPU baseline)
+#   bench                  the default config's `python bench.py --full` line (with the CPU baseline)
 #   bench=<c1,c2,..>       `bench.py --config <c>` lines (no CPU baseline)
 #   shares=<c1,c2,..>      one GPU's share of the 2-, 4- and 8-way strong split next to the whole problem
 #   ab=<cfg>[@<B,Hq,Hkv,S,D,dtype,causal>]
@@ -44,7 +44,7 @@ for ph in "$@"; do
       tail -1 "$OUT/smoke.log" ;;
     bench)
       if [ -z "$arg" ]; then
-        timeout -k 10 300 python bench.py > "$OUT/default_bench.json" 2> "$OUT/default_bench.err" || fail bench "$OUT/default_bench.err"
+        timeout -k 10 300 python bench.py --full > "$OUT/default_bench.json" 2> "$OUT/default_bench.err" || fail bench "$OUT/default_bench.err"
         cut -c1-300 "$OUT/default_bench.json"
       else
         for c in ${arg//,/ }; do

@@ -97,6 +97,46 @@ def test_algorithmic_counts_of_the_headline_config():
     assert bench.algo_bytes(c) == 536870912  # q, k, v, o once each
 
 
+# ---- --dump-outputs: what a step returned, as float32 .npy files within a byte budget ----
+def test_dump_outputs_writes_small_outputs_whole(tmp_path):
+    import numpy as np
+    import torch
+
+    t = torch.randn(2, 3, 5, 8, generator=torch.Generator().manual_seed(0)).half()
+    info = bench.dump_outputs(t, tmp_path / "one")
+    a = np.load(tmp_path / "one" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 5, 8) and np.array_equal(a, t.float().numpy())
+    assert info == {"out": {"shape": [2, 3, 5, 8]}}
+    # a step of several calls (a rank's shard runs): one file per call, in order
+    bench.dump_outputs([t, t[:1] * 2], tmp_path / "two", suffix="_rank1")
+    assert sorted(p.name for p in (tmp_path / "two").iterdir()) == ["out_0_rank1.npy", "out_1_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "two" / "out_1_rank1.npy"), (t[:1] * 2).float().numpy())
+
+
+def test_dump_outputs_samples_the_same_rows_of_a_larger_output(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 40 * 16 * 4)  # two outputs: 40 rows of 16 floats each
+    t = torch.randn(3, 100, 16, generator=torch.Generator().manual_seed(1)).bfloat16()
+    info = bench.dump_outputs([t, t + 1], tmp_path / "a")
+    bench.dump_outputs([t, t + 1], tmp_path / "b")
+    a0, a1, b0 = (np.load(tmp_path / d / f) for d, f in (("a", "out_0.npy"), ("a", "out_1.npy"), ("b", "out_0.npy")))
+    assert a0.dtype == np.float32 and a0.shape == (40, 16) and a1.shape == (40, 16)
+    assert np.array_equal(a0, b0)  # the same rows on every run
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 2 * 40 * 16 * 4 + 2 * 128
+    # every sampled row is a whole row of the output, each at most once, in row order
+    full = t.float().numpy().reshape(-1, 16)
+    rows = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a0]
+    assert rows == sorted(set(rows)) and len(rows) == 40
+    assert np.array_equal(a1, (t + 1).float().numpy().reshape(-1, 16)[rows])  # the same rows of each output
+    assert info["out_0"] == {"shape": [3, 100, 16], "rows_sampled": 40, "of": 300}
+
+
+def test_dump_budget_stays_under_64_mb():
+    assert bench.DUMP_BYTES + 64 * 1024 <= 64_000_000
+
+
 # ---- multi-GPU mode of bench.py: strong split by default, one rank's share alone ----
 import os  # noqa: E402
 import socket  # noqa: E402
