@@ -6,3 +6,4 @@ the reference's submodule paths ``flash_attention.flash_attention`` and
 """
 from .flash_attention import flash_attn_func  # noqa: F401
 from .flash_attention import flash_attn_varlen_func  # noqa: F401  (beyond the reference: varlen)
+from .flash_attention import flash_attn_paged_func  # noqa: F401  (beyond the reference: paged KV cache)

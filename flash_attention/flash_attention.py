@@ -22,6 +22,7 @@ from flash_attention_cute_amd.flash_attention import (  # noqa: F401
     flash_attn_func,
 )
 from flash_attention_cute_amd.flash_attention import flash_attn_varlen_func  # noqa: F401  (beyond the reference)
+from flash_attention_cute_amd.flash_attention import flash_attn_paged_func  # noqa: F401  (beyond the reference)
 
 from .load_cpp_extention import load_extension  # noqa: F401  (the reference module imports it, :2)
 

@@ -389,6 +389,10 @@ def hazards(text: str) -> list[str]:
 
 def check_file(path) -> list[str]:
     text = open(path).read()
+    if "fa_paged_inst" in str(path):  # the paged decode kernels (csrc/fa_paged_inst.hip): no fa_fwd_w4 there
+        if "fa_decode_paged" not in text:
+            return [f"{path}: no fa_decode_paged kernel in the assembly (stale or wrong file)"]
+        return spills(text)
     if "fa_fwd_w4" not in text:
         return [f"{path}: no fa_fwd_w4 kernel in the assembly (stale or wrong file)"]
     return agpr_violations(text) + spills(text) + hazards(text)

@@ -6,9 +6,10 @@ files into the source tree. Here nothing is hipified: two explicit compiler invo
 into the package directory so the artefacts travel with the repository snapshot.
 
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
-     head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_fwd_gfx950.hip (C-ABI
-     dispatcher)  ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h; no torch
-     symbols)
+     head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_paged_inst.hip x 16 (the
+     paged decode kernels, the same combinations) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip
+     (C-ABI dispatchers)  ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h and
+     include/fa_gfx950_paged.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -143,7 +144,22 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
                       f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
                       "-Wno-inline-asm", "-c", CSRC / "fa_inst.hip", "-o", obj], obj, inst_deps + tooling))
-    for src in ("fa_fwd_gfx950.hip", "fa_rope.hip"):  # C-ABI dispatcher, standalone RoPE kernel
+    # the paged decode kernels (csrc/fa_paged_inst.hip), one translation unit per combination as well, in
+    # directories of their own: the dense instantiations above compile exactly as without them
+    paged_deps = inst_deps + [CSRC / "fa_paged_inst.hip"]
+    for dt, c, d, e in INSTANCES:
+        idir = objdir / f"paged_{dt.lower()}_c{c}_d{d}_x{e}"
+        idir.mkdir(parents=True, exist_ok=True)
+        obj = idir / "fa_paged_inst.o"
+        objs.append(obj)
+        stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
+        if not stub:
+            asm_files.append(idir / f"fa_paged_inst-hip-amdgcn-amd-amdhsa-{ARCH}.s")
+        cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
+                      f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
+                      "-Wno-inline-asm", "-c", CSRC / "fa_paged_inst.hip", "-o", obj], obj, paged_deps + tooling))
+    # C-ABI dispatchers (dense, paged), standalone RoPE kernel
+    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_rope.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src, "-o", obj], obj,
@@ -153,7 +169,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         stamp = obj.with_suffix(".cmd")
         line = " ".join(map(str, cmd))
         if (not force and not _stale(obj, deps) and stamp.exists() and stamp.read_text() == line
-                and (obj.name != "fa_inst.o" or next(obj.parent.glob("*.s"), None) is not None)):
+                and (obj.name not in ("fa_inst.o", "fa_paged_inst.o") or next(obj.parent.glob("*.s"), None) is not None)):
             return
         _run(cmd, verbose)
         stamp.write_text(line)
@@ -170,7 +186,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         # (gate=False: an experiment that reproduces a rejected build, e.g. FA_EXP_CZERO, rule R5)
         problems = [q for q in problems if "vgpr_spill_count" not in q] if gate else []
     for a in asm_files:  # keep the .s for inspection, drop the large intermediates
-        for junk in a.parent.glob("fa_inst*"):
+        for junk in a.parent.glob("fa_*inst*"):
             if junk.suffix in (".bc", ".hipi", ".out", ".txt", ".hipfb") or junk.name.endswith("resolution.txt"):
                 junk.unlink()
     if problems:
@@ -189,7 +205,7 @@ def build_ext(force: bool = False, verbose: bool = False) -> Path:
     lib = build_abi(force=force, verbose=verbose)
     out = ext_path()
     src = CSRC / "flash_attention_api.cpp"
-    if not force and not _stale(out, [src, INCLUDE / "fa_gfx950.h", lib]):
+    if not force and not _stale(out, [src, INCLUDE / "fa_gfx950.h", INCLUDE / "fa_gfx950_paged.h", lib]):
         return out
     incs = cpp_extension.include_paths(device_type="cuda")
     libdirs = cpp_extension.library_paths(device_type="cuda")

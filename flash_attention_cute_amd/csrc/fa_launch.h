@@ -63,7 +63,7 @@ inline int variant_from_env() { return knobs().variant; }
 
 // Which kernel the last fa_fwd_gfx950* call on this thread launched (fa_debug_last_path)
 enum Path { kPathNone = 0, kPathW4 = 1, kPathW8 = 2, kPathW4Slow = 3, kPathDecode = 4, kPathDecodeSplit = 5, kPathP8 = 6,
-            kPathM32 = 7, kPathM16 = 8 };
+            kPathM32 = 7, kPathM16 = 8, kPathDecodePaged = 9, kPathDecodePagedSplit = 10 };
 void set_last_path(int path);
 void set_last_zigzag(int z);
 void set_last_dec_fused(bool fused);  // (fa_debug_last_dec_fused: the last decode launch merged in-kernel)

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "fa_gfx950.h"
+#include "fa_gfx950_paged.h"
 
 namespace flash_attention {
 
@@ -556,6 +557,114 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
     return o;
 }
 
+// Paged KV-cache decode (include/fa_gfx950_paged.h fa_fwd_gfx950_paged): q [B, Hq, Sq, D] dense, the
+// caches page pools [num_pages, Hkv, page_size, D] (any strides, last dim contiguous; page_size a
+// multiple of 32), block_table int32 [B, max_pages], cache_seqlens int32 [B], both on the device. The
+// pool is read in place: no gather, no host synchronisation (graph-capturable). Decode shapes only
+// (g * Sq <= 64; the Python op gathers larger query blocks); Sq == 1 takes the q-head pack of
+// flash_attention_fwd. No reference counterpart.
+torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                        torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                        float softmax_scale, bool causal) {
+    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
+                "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(q.size(3) == k_cache.size(3), "q and the caches must have the same hidden dimension");
+    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0, "q must have at least one element");
+    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
+    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
+                "number of heads in q must be multiple of number of heads in k and v");
+    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
+    TORCH_CHECK(q.dtype() == k_cache.dtype() && q.dtype() == v_cache.dtype(), "q, k, v must have the same data type");
+    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
+                "q, k, v only support fp16 or bf16 data type");
+    TORCH_CHECK(q.stride(3) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
+                "q, k, v must be contiguous in the last dimension");
+    TORCH_CHECK(q.size(3) % 8 == 0, "hidden dimension must be multiple of 8");
+    TORCH_CHECK(q.size(3) <= 128, "only support hidden dimension <= 128");
+    TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda(), "q, k, v must be on CUDA device");
+    TORCH_CHECK(q.device() == k_cache.device() && q.device() == v_cache.device(),
+                "q, k, v must be on the same CUDA device");
+    const int64_t bs = q.size(0);
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
+                    block_table.size(1) > 0,
+                "block_table must be int32 [batch, max_pages]");
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
+                "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(block_table.device() == q.device() && cache_seqlens.device() == q.device(),
+                "block_table and cache_seqlens must be on the device of q");
+    c10::DeviceGuard device_guard(q.device());
+    TORCH_CHECK(device_is_gfx950(q.device().index()),
+                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+
+    // the pool is read where it is; only a pool whose strides are not 16-byte multiples is copied
+    torch::Tensor qx = aligned16(q) ? q : q.contiguous();
+    torch::Tensor kx = aligned16(k_cache) ? k_cache : k_cache.contiguous();
+    torch::Tensor vx = aligned16(v_cache) ? v_cache : v_cache.contiguous();
+    torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
+    torch::Tensor sl = cache_seqlens.contiguous();
+
+    int64_t head_q = qx.size(1), seqlen_q = qx.size(2);
+    const int64_t head_kv = kx.size(1), headdim = qx.size(3), g = head_q / head_kv;
+    // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
+    const bool pack = seqlen_q == 1;
+    if (pack) {
+        head_q = head_kv;
+        seqlen_q = g;
+        causal = false;
+        qx = qx.reshape({bs, head_q, seqlen_q, headdim});
+        if (!aligned16(qx)) qx = qx.contiguous();
+    }
+    auto o = torch::empty_like(qx);
+    if (!aligned16(o)) o = torch::empty(qx.sizes(), qx.options());
+
+    fa_paged_params pp;
+    fa_fwd_params &params = pp.base;
+    params.q_ptr = qx.data_ptr();
+    params.k_ptr = kx.data_ptr();
+    params.v_ptr = vx.data_ptr();
+    params.o_ptr = o.data_ptr();
+    params.batch_size = bs;
+    params.num_heads_q = head_q;
+    params.num_heads_kv = head_kv;
+    params.seqlen_q = seqlen_q;
+    params.seqlen_kv = bt.size(1) * kx.size(2);
+    params.headdim = headdim;
+    params.head_q_per_group = pack ? 1 : g;
+    params.q_batch_stride = stride_or_zero(qx, 0);
+    params.k_batch_stride = stride_or_zero(kx, 0);  // the page stride
+    params.v_batch_stride = stride_or_zero(vx, 0);
+    params.o_batch_stride = stride_or_zero(o, 0);
+    params.q_head_stride = stride_or_zero(qx, 1);
+    params.k_head_stride = stride_or_zero(kx, 1);
+    params.v_head_stride = stride_or_zero(vx, 1);
+    params.o_head_stride = stride_or_zero(o, 1);
+    params.q_seqlen_stride = stride_or_zero(qx, 2);
+    params.k_seqlen_stride = kx.stride(2);
+    params.v_seqlen_stride = vx.stride(2);
+    params.o_seqlen_stride = stride_or_zero(o, 2);
+    softmax_scale *= M_LOG2E;
+    params.softmax_scale = softmax_scale;
+    pp.block_table = bt.data_ptr<int32_t>();
+    pp.block_table_stride = bt.stride(0);
+    pp.max_pages = bt.size(1);
+    pp.num_pages = kx.size(0);
+    pp.page_size = kx.size(2);
+    pp.seqlens_k = sl.data_ptr<int32_t>();
+
+    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
+    void *stream = c10::hip::getCurrentHIPStream(qx.device().index()).stream();
+    const int64_t ws_bytes = fa_fwd_gfx950_paged_workspace_size(&pp, dtype, causal ? 1 : 0);
+    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_workspace_size failed: ", fa_last_error());
+    torch::Tensor ws;
+    if (ws_bytes > 0) ws = torch::empty({ws_bytes}, qx.options().dtype(torch::kUInt8));
+    const int rc = fa_fwd_gfx950_paged(&pp, dtype, causal ? 1 : 0, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
+                                       stream);
+    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_paged failed (code ", rc, "): ", fa_last_error());
+    if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
+    return o;
+}
+
 }  // namespace flash_attention
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -569,6 +678,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "FlashAttention-2 forward with a local (sliding) window of window_left + 1 keys, gfx950");
     m.def("flash_attention_padded_fwd", &flash_attention::flash_attention_padded_fwd,
           "FlashAttention-2 forward over padded batches (per-sequence query / key ranges in dense tensors), gfx950");
+    m.def("flash_attention_paged_fwd", &flash_attention::flash_attention_paged_fwd,
+          "FlashAttention-2 decode over a paged KV cache (block table, per-sequence lengths), gfx950");
     m.def("rope_apply", &flash_attention::rope_apply, "rotate-half RoPE, one HIP pass (gfx950)");
     m.def("abi_version", []() { return fa_abi_version(); });
+    m.def("paged_version", []() { return fa_paged_version(); });
 }

@@ -410,3 +410,109 @@ def flash_attn_window_func(q, k, v, window_left, softmax_scale=None, causal=Fals
     -1)``)."""
     softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
     return torch.ops.flash_attention.window_forward(q, k, v, int(window_left), softmax_scale, causal)
+
+
+# ---------------------------------------------------------------------------------------------
+# Paged KV cache -- block-table attention on the split-KV decode kernel (include/fa_gfx950_paged.h
+# fa_fwd_gfx950_paged); no reference counterpart (the reference has no KV cache). The layout of
+# vLLM-style engines and flash-attn's flash_attn_with_kvcache(..., block_table=...): the caches are
+# page pools [num_pages, Hkv, page_size, D], sequence b's key n is row n % page_size of page
+# block_table[b][n / page_size], and it has cache_seqlens[b] keys.
+# ---------------------------------------------------------------------------------------------
+_PAGED_DECODE_MAX_ROWS = 64  # csrc/fa_launch.h kDecMaxRows: (q-head, position) rows per kv-head
+
+
+def _gather_pages(cache: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    """The table's pages as a dense [B, Hkv, max_pages * page_size, D] (a copy; ids clamped into the pool
+    as the kernel clamps them, so unused entries may hold anything)."""
+    b, max_pages = block_table.shape
+    num_pages, hkv, page_size, d = cache.shape
+    ids = block_table.reshape(-1).clamp(0, num_pages - 1).to(torch.int64)
+    pages = cache.index_select(0, ids).reshape(b, max_pages, hkv, page_size, d)
+    return pages.transpose(1, 2).reshape(b, hkv, max_pages * page_size, d)
+
+
+@torch.library.custom_op("flash_attention::paged_forward", mutates_args=())
+def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                  block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                  softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    # q: [B, Hq, Sq, D] (each sequence's last Sq positions); caches: [num_pages, Hkv, page_size, D];
+    # block_table: int32 [B, max_pages]; cache_seqlens: int32 [B]. Non-GPU default: per-sequence gather
+    # of the sequence's pages + torch SDPA with the kernel's semantics (bottom-right causal per sequence,
+    # GQA, rows with no visible key 0, lengths clamped to the table's capacity).
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    out = torch.zeros_like(q)
+    sq = q.size(2)
+    num_pages, _, page_size, _ = k_cache.shape
+    cap = block_table.size(1) * page_size
+    for b, n in enumerate(cache_seqlens.tolist()):
+        n = min(max(n, 0), cap)
+        if n == 0:
+            continue
+        ids = block_table[b, :(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
+        kb = k_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
+        vb = v_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
+        mask = _bottom_right_causal(sq, n, q.device) if causal else None
+        o = torch.nn.functional.scaled_dot_product_attention(q[b:b + 1], kb, vb, attn_mask=mask, scale=softmax_scale,
+                                                             enable_gqa=True)
+        if mask is not None:
+            o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
+        out[b:b + 1] = o
+    return out
+
+
+@torch.library.register_kernel("flash_attention::paged_forward", "cuda")
+def flash_attention_paged_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                       block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                       softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    if flash_attention_cuda is None:
+        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    g, sq = q.size(1) // k_cache.size(1), q.size(2)
+    if g * sq > _PAGED_DECODE_MAX_ROWS:
+        # the copying path: the kernel serves decode shapes only, larger query blocks (a chunked prefill
+        # on a paged cache) gather the table's pages into a dense cache for the padded entry. No host
+        # synchronisation either, so it stays graph-capturable.
+        k = _gather_pages(k_cache, block_table)
+        v = _gather_pages(v_cache, block_table)
+        return flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None,
+                                                   None, softmax_scale, causal, -1)
+    head_dim = q.size(3)
+    need_padding = head_dim % 8 != 0
+    if need_padding:  # (pads the pool: a copy of it)
+        pad = [0, 8 - head_dim % 8]
+        q = torch.nn.functional.pad(q, pad)
+        k_cache = torch.nn.functional.pad(k_cache, pad)
+        v_cache = torch.nn.functional.pad(v_cache, pad)
+    q = q.contiguous() if q.stride(3) != 1 else q
+    k_cache = k_cache.contiguous() if k_cache.stride(3) != 1 else k_cache
+    v_cache = v_cache.contiguous() if v_cache.stride(3) != 1 else v_cache
+    attn = flash_attention_cuda.flash_attention_paged_fwd(q, k_cache, v_cache, block_table, cache_seqlens,
+                                                          softmax_scale, causal)
+    if need_padding:
+        attn = attn[:, :, :, :head_dim]
+    return attn
+
+
+@torch.library.register_fake("flash_attention::paged_forward")
+def flash_attention_paged_forward_fake(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None,
+                                       causal=False):
+    return torch.empty_like(q)
+
+
+def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False):
+    """Attention of q [B, Hq, Sq, D] -- each sequence's LAST Sq positions -- over a paged KV cache:
+    ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] with any strides (flash-attn's
+    [num_pages, page_size, Hkv, D] is ``cache.transpose(1, 2)``), ``page_size`` a multiple of 32;
+    ``block_table`` int32 [B, max_pages] and ``cache_seqlens`` int32 [B] on q's device. Sequence b's key n
+    is row ``n % page_size`` of page ``block_table[b, n // page_size]``. Lengths are clamped to
+    ``[0, max_pages * page_size]`` and page ids into the pool on the device; entries of pages a sequence
+    does not reach, and the rows of its last page past its end, are never read. Causal masks are
+    bottom-right aligned per sequence; a sequence without keys gives 0 rows.
+
+    Decode shapes (``Hq / Hkv * Sq <= 64``) read the pool in place with the paged split-KV kernel. Larger
+    query blocks take the COPYING path: the table's pages are gathered into a dense cache
+    (``index_select``) for ``flash_attn_padded_func``. Neither path synchronises with the host, so both
+    can be captured in a graph."""
+    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    return torch.ops.flash_attention.paged_forward(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale,
+                                                   causal)
