@@ -7,3 +7,5 @@ the reference's submodule paths ``flash_attention.flash_attention`` and
 from .flash_attention import flash_attn_func  # noqa: F401
 from .flash_attention import flash_attn_varlen_func  # noqa: F401  (beyond the reference: varlen)
 from .flash_attention import flash_attn_paged_func  # noqa: F401  (beyond the reference: paged KV cache)
+from .flash_attention import flash_attn_kvcache_append, flash_attn_with_kvcache  # noqa: F401  (beyond the reference)
+from .flash_attention import flash_attention_kvcache_append  # noqa: F401  (the custom op's function)

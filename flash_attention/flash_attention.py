@@ -23,6 +23,11 @@ from flash_attention_cute_amd.flash_attention import (  # noqa: F401
 )
 from flash_attention_cute_amd.flash_attention import flash_attn_varlen_func  # noqa: F401  (beyond the reference)
 from flash_attention_cute_amd.flash_attention import flash_attn_paged_func  # noqa: F401  (beyond the reference)
+from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond the reference: KV-cache append)
+    flash_attention_kvcache_append,
+    flash_attn_kvcache_append,
+    flash_attn_with_kvcache,
+)
 
 from .load_cpp_extention import load_extension  # noqa: F401  (the reference module imports it, :2)
 

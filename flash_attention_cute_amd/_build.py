@@ -8,8 +8,9 @@ into the package directory so the artefacts travel with the repository snapshot.
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
      head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_paged_inst.hip x 16 (the
      paged decode kernels, the same combinations) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip
-     (C-ABI dispatchers)  ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h and
-     include/fa_gfx950_paged.h; no torch symbols)
+     (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip (stand-alone kernels with their entries)
+     ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h and
+     include/fa_gfx950_kvcache.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -158,8 +159,8 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
                       f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
                       "-Wno-inline-asm", "-c", CSRC / "fa_paged_inst.hip", "-o", obj], obj, paged_deps + tooling))
-    # C-ABI dispatchers (dense, paged), standalone RoPE kernel
-    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_rope.hip"):
+    # C-ABI dispatchers (dense, paged), standalone RoPE kernel, KV-cache append kernel
+    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src, "-o", obj], obj,
@@ -205,7 +206,8 @@ def build_ext(force: bool = False, verbose: bool = False) -> Path:
     lib = build_abi(force=force, verbose=verbose)
     out = ext_path()
     src = CSRC / "flash_attention_api.cpp"
-    if not force and not _stale(out, [src, INCLUDE / "fa_gfx950.h", INCLUDE / "fa_gfx950_paged.h", lib]):
+    if not force and not _stale(out, [src, INCLUDE / "fa_gfx950.h", INCLUDE / "fa_gfx950_paged.h",
+                                      INCLUDE / "fa_gfx950_kvcache.h", lib]):
         return out
     incs = cpp_extension.include_paths(device_type="cuda")
     libdirs = cpp_extension.library_paths(device_type="cuda")

@@ -37,6 +37,23 @@ class FaFwdParams(ctypes.Structure):
                 + [("softmax_scale", ctypes.c_float)])
 
 
+_P, _I = ctypes.c_void_p, ctypes.c_int64
+
+
+class FaKvcacheParams(ctypes.Structure):
+    """include/fa_gfx950_kvcache.h ``fa_kvcache_params`` (the raw ABI of the KV-cache append, for tests)."""
+
+    _fields_ = ([("k_new", _P), ("v_new", _P)]
+                + [(f"{t}n_{s}_stride", _I) for t in "kv" for s in ("batch", "head", "seqlen")]
+                + [("q", _P), ("q_out", _P)]
+                + [(f"{t}_{s}_stride", _I) for t in ("q", "qo") for s in ("batch", "head", "seqlen")]
+                + [("cos", _P), ("sin", _P), ("cs_row_stride", _I), ("max_pos", _I), ("k_cache", _P), ("v_cache", _P)]
+                + [(f"{t}_{s}_stride", _I) for t in "kv" for s in ("page", "head", "row")]
+                + [("block_table", _P), ("block_table_stride", _I), ("max_pages", _I), ("num_pages", _I),
+                   ("page_size", _I), ("seqlens_k", _P), ("seqlens_out", _P)]
+                + [(n, _I) for n in ("batch_size", "num_heads_q", "num_heads_kv", "seqlen_new", "seqlen_q", "headdim")])
+
+
 def lib(debug: bool = False) -> ctypes.CDLL:
     """The already-loaded libfa_gfx950.so (the torch binding links it; dlopen returns that handle), or
     (``debug``) lib/libfa_gfx950_debug.so."""
@@ -74,6 +91,8 @@ def lib(debug: bool = False) -> ctypes.CDLL:
         lib.fa_fwd_gfx950_workspace_size.restype = ctypes.c_int64
         lib.fa_fwd_gfx950_ws.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_void_p]
+        lib.fa_kvcache_append_gfx950.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        lib.fa_kvcache_append_gfx950_check.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _libs[debug] = lib
     return _libs[debug]
 

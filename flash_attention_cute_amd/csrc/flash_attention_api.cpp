@@ -18,11 +18,14 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "fa_gfx950.h"
+#include "fa_gfx950_kvcache.h"
 #include "fa_gfx950_paged.h"
 
 namespace flash_attention {
@@ -665,6 +668,152 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     return o;
 }
 
+// In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
+// k / v [B, Hkv, Sn, D] are written at positions cache_seqlens[b] + i of the paged ([num_pages, Hkv,
+// page_size, D] + block_table int32 [B, max_pages]) or dense ([B, Hkv, Smax, D], no table) cache, k rotated
+// at those positions when the [max_pos, D] tables are given; q [B, Hq, Sq, D] is rotated at the sequence's
+// last Sq positions after the append. Returns (new_seqlens int32 [B], q_rot or an empty tensor). The caches
+// are written where they are -- never copied, whatever their alignment -- in one launch with no host
+// synchronisation (graph-capturable). No reference counterpart.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
+    torch::Tensor &k_cache, torch::Tensor &v_cache, c10::optional<torch::Tensor> k, c10::optional<torch::Tensor> v,
+    torch::Tensor &cache_seqlens, c10::optional<torch::Tensor> block_table, c10::optional<torch::Tensor> q,
+    c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin) {
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4,
+                "the caches must be 4-D [pages, heads, page_size, dim] or [batch, heads, seqlen, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(k_cache.dtype() == v_cache.dtype(), "k_cache, v_cache must have the same data type");
+    TORCH_CHECK(k_cache.dtype() == torch::kHalf || k_cache.dtype() == torch::kBFloat16,
+                "the caches only support fp16 or bf16 data type");
+    TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.device() == v_cache.device(),
+                "the caches must be on the same CUDA device");
+    TORCH_CHECK(k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
+                "the caches must be contiguous in the last dimension (they are written in place, never copied)");
+    TORCH_CHECK(k_cache.size(1) > 0 && k_cache.size(2) > 0 && k_cache.size(3) > 0,
+                "the caches must have at least one head, one row and one element per row");
+    TORCH_CHECK(k.has_value() == v.has_value(), "k and v must be given together");
+    TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be given together");
+    TORCH_CHECK(!q.has_value() || rotary_cos.has_value(), "q is rotated only: it needs rotary_cos / rotary_sin");
+    const int64_t bs = cache_seqlens.dim() == 1 ? cache_seqlens.size(0) : -1;
+    const int64_t hkv = k_cache.size(1), d = k_cache.size(3);
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && bs >= 0, "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(cache_seqlens.device() == k_cache.device(), "cache_seqlens must be on the device of the caches");
+    const bool paged = block_table.has_value();
+    if (paged) {
+        TORCH_CHECK(block_table->dtype() == torch::kInt32 && block_table->dim() == 2 && block_table->size(0) == bs &&
+                        block_table->size(1) > 0,
+                    "block_table must be int32 [batch, max_pages]");
+        TORCH_CHECK(block_table->device() == k_cache.device(), "block_table must be on the device of the caches");
+        TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
+    } else {
+        TORCH_CHECK(k_cache.size(0) == bs, "a dense cache must have cache_seqlens' batch size");
+    }
+    auto check_new = [&](const torch::Tensor &t, const char *name, int64_t heads_multiple_of) {
+        TORCH_CHECK(t.dim() == 4 && t.size(0) == bs && t.size(3) == d, name, " must be [batch, heads, seqlen, dim] "
+                    "with the batch of cache_seqlens and the caches' hidden dimension");
+        TORCH_CHECK(t.size(1) > 0 && t.size(1) % heads_multiple_of == 0, name, ": wrong number of heads");
+        TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+        TORCH_CHECK(t.device() == k_cache.device(), name, " must be on the device of the caches");
+        TORCH_CHECK(t.stride(3) == 1, name, " must be contiguous in the last dimension");
+    };
+    int64_t sn = 0, sq = 0, hq = 0;
+    if (k.has_value()) {
+        check_new(*k, "k", hkv);
+        check_new(*v, "v", hkv);
+        TORCH_CHECK(k->size(1) == hkv && k->sizes() == v->sizes(), "k, v must have the caches' number of heads");
+        sn = k->size(2);
+    }
+    if (q.has_value()) {
+        check_new(*q, "q", hkv);
+        hq = q->size(1);
+        sq = q->size(2);
+    }
+    torch::Tensor cs, sn_t;
+    if (rotary_cos.has_value()) {
+        TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
+        auto table = [&](const torch::Tensor &t, const char *name) {
+            TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
+            TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+            TORCH_CHECK(t.device() == k_cache.device(), name, " must be on the device of the caches");
+            return t.stride(1) == 1 ? t : t.contiguous();
+        };
+        cs = table(*rotary_cos, "rotary_cos");
+        sn_t = table(*rotary_sin, "rotary_sin");
+        TORCH_CHECK(cs.size(0) == sn_t.size(0), "rotary_cos and rotary_sin must have the same number of rows");
+        if (cs.size(0) > 1 && cs.stride(0) != sn_t.stride(0)) {
+            cs = cs.contiguous();
+            sn_t = sn_t.contiguous();
+        }
+    }
+    c10::DeviceGuard device_guard(k_cache.device());
+    TORCH_CHECK(device_is_gfx950(k_cache.device().index()),
+                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+
+    const int64_t page_size = k_cache.size(2), max_pages = paged ? block_table->size(1) : 1;
+    torch::Tensor q_rot = q.has_value() ? torch::empty(q->sizes(), q->options()) : torch::empty({0}, k_cache.options());
+    if (bs == 0 || (sn == 0 && sq == 0))  // nothing to launch: the lengths, clamped as the kernel clamps them
+        return {cache_seqlens.clamp(0, max_pages * page_size), q_rot};
+    torch::Tensor sl = cache_seqlens.contiguous();
+    torch::Tensor new_seqlens = torch::empty({bs}, sl.options());
+    torch::Tensor bt;
+    if (paged) bt = block_table->stride(1) == 1 ? *block_table : block_table->contiguous();
+
+    fa_kvcache_params p;
+    memset(&p, 0, sizeof(p));
+    if (sn > 0) {
+        p.k_new = k->data_ptr();
+        p.v_new = v->data_ptr();
+        p.kn_batch_stride = stride_or_zero(*k, 0);
+        p.kn_head_stride = stride_or_zero(*k, 1);
+        p.kn_seqlen_stride = stride_or_zero(*k, 2);
+        p.vn_batch_stride = stride_or_zero(*v, 0);
+        p.vn_head_stride = stride_or_zero(*v, 1);
+        p.vn_seqlen_stride = stride_or_zero(*v, 2);
+    }
+    if (sq > 0) {
+        p.q = q->data_ptr();
+        p.q_out = q_rot.data_ptr();
+        p.q_batch_stride = stride_or_zero(*q, 0);
+        p.q_head_stride = stride_or_zero(*q, 1);
+        p.q_seqlen_stride = stride_or_zero(*q, 2);
+        p.qo_batch_stride = stride_or_zero(q_rot, 0);
+        p.qo_head_stride = stride_or_zero(q_rot, 1);
+        p.qo_seqlen_stride = stride_or_zero(q_rot, 2);
+    }
+    if (cs.defined()) {
+        p.cos = cs.data_ptr();
+        p.sin = sn_t.data_ptr();
+        p.cs_row_stride = stride_or_zero(cs, 0);
+        p.max_pos = cs.size(0);
+    }
+    p.k_cache = k_cache.data_ptr();
+    p.v_cache = v_cache.data_ptr();
+    p.k_page_stride = stride_or_zero(k_cache, 0);
+    p.k_head_stride = stride_or_zero(k_cache, 1);
+    p.k_row_stride = stride_or_zero(k_cache, 2);
+    p.v_page_stride = stride_or_zero(v_cache, 0);
+    p.v_head_stride = stride_or_zero(v_cache, 1);
+    p.v_row_stride = stride_or_zero(v_cache, 2);
+    p.block_table = paged ? bt.data_ptr<int32_t>() : nullptr;
+    p.block_table_stride = paged ? bt.stride(0) : 0;
+    p.max_pages = max_pages;
+    p.num_pages = k_cache.size(0);
+    p.page_size = page_size;
+    p.seqlens_k = sl.data_ptr<int32_t>();
+    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
+    p.batch_size = bs;
+    p.num_heads_q = hq;
+    p.num_heads_kv = hkv;
+    p.seqlen_new = sn;
+    p.seqlen_q = sq;
+    p.headdim = d;
+    const int dtype = k_cache.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
+    void *stream = c10::hip::getCurrentHIPStream(k_cache.device().index()).stream();
+    const int rc = fa_kvcache_append_gfx950(&p, dtype, stream);
+    TORCH_CHECK(rc == FA_OK, "fa_kvcache_append_gfx950 failed (code ", rc, "): ", fa_last_error());
+    return {new_seqlens, q_rot};
+}
+
 }  // namespace flash_attention
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -683,4 +832,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rope_apply", &flash_attention::rope_apply, "rotate-half RoPE, one HIP pass (gfx950)");
     m.def("abi_version", []() { return fa_abi_version(); });
     m.def("paged_version", []() { return fa_paged_version(); });
+    m.def("flash_attention_kvcache_append", &flash_attention::flash_attention_kvcache_append,
+          "In-place KV-cache append (paged or dense) with fused rotate-half RoPE of k and q, one HIP launch (gfx950)");
+    m.def("kvcache_version", []() { return fa_kvcache_version(); });
 }

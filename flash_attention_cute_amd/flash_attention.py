@@ -516,3 +516,136 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
     return torch.ops.flash_attention.paged_forward(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale,
                                                    causal)
+
+
+# ---------------------------------------------------------------------------------------------
+# KV-cache append -- the write side of the paged / dense cache, with RoPE fused in
+# (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950); no reference counterpart. The append half of
+# flash-attn's flash_attn_with_kvcache: new token i of sequence b goes to position n = cache_seqlens[b]
+# + i, i.e. row n % page_size of page block_table[b][n / page_size] (dense cache: row n of batch row b).
+# A write is dropped, never redirected: positions past the capacity and page ids outside the pool.
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("flash_attention::kvcache_append", mutates_args=("k_cache", "v_cache"))
+def flash_attention_kvcache_append(k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
+                                   v: Optional[torch.Tensor], cache_seqlens: torch.Tensor,
+                                   block_table: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                                   rotary_cos: Optional[torch.Tensor] = None,
+                                   rotary_sin: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    # caches: [num_pages, Hkv, page_size, D] with block_table int32 [B, max_pages], or dense [B, Hkv, Smax,
+    # D] without; k, v: [B, Hkv, Sn, D] (or None); q: [B, Hq, Sq, D] (or None); rotary_*: [max_pos, D].
+    # Non-GPU default: the kernel's semantics token by token, with the same drop rules.
+    if q is not None and rotary_cos is None:
+        raise ValueError("q is rotated only: it needs rotary_cos / rotary_sin")
+    num_pages, _, page_size, _ = k_cache.shape
+    max_pages = block_table.size(1) if block_table is not None else 1
+    cap = max_pages * page_size
+    sn = k.size(2) if k is not None else 0
+    lens = [min(max(n, 0), cap) for n in cache_seqlens.tolist()]
+    new_lens = [min(n + sn, cap) for n in lens]
+    table = block_table.tolist() if block_table is not None else None
+    rope = rotary_cos is not None
+    if rope:
+        cos, sin = rotary_cos.to(k_cache.dtype), rotary_sin.to(k_cache.dtype)
+        max_pos = cos.size(0)
+    for b, n0 in enumerate(lens):
+        for i in range(sn):
+            n = n0 + i
+            if n >= cap:
+                continue  # past the table's capacity: dropped
+            page = table[b][n // page_size] if table is not None else b
+            if page < 0 or page >= num_pages:
+                continue  # outside the pool: dropped, never clamped
+            kr = k[b:b + 1, :, i:i + 1]
+            if rope:
+                pos = min(n, max_pos - 1)
+                kr = _rope_reference(kr, cos[pos:pos + 1], sin[pos:pos + 1])
+            k_cache[page, :, n % page_size] = kr[0, :, 0]
+            v_cache[page, :, n % page_size] = v[b, :, i]
+    if q is None:
+        q_rot = k_cache.new_empty(0)
+    else:
+        sq = q.size(2)
+        pos = torch.tensor([[min(max(e - sq + i, 0), max_pos - 1) for i in range(sq)] for e in new_lens],
+                           dtype=torch.int64, device=q.device).reshape(-1, sq)
+        q_rot = _rope_reference(q, cos[pos], sin[pos])
+    return torch.tensor(new_lens, dtype=torch.int32, device=cache_seqlens.device), q_rot
+
+
+@torch.library.register_kernel("flash_attention::kvcache_append", "cuda")
+def flash_attention_kvcache_append_cuda(k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
+                                        v: Optional[torch.Tensor], cache_seqlens: torch.Tensor,
+                                        block_table: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                                        rotary_cos: Optional[torch.Tensor] = None,
+                                        rotary_sin: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    if flash_attention_cuda is None:
+        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    # the inputs may be copied to make their last dimension contiguous; the caches never are (a copy would
+    # swallow the write): the binding rejects a cache whose last dimension is not contiguous
+    k, v, q = (t.contiguous() if t is not None and t.stride(3) != 1 else t for t in (k, v, q))
+    if rotary_cos is not None:
+        rotary_cos, rotary_sin = rotary_cos.to(k_cache.dtype), rotary_sin.to(k_cache.dtype)
+    new_seqlens, q_rot = flash_attention_cuda.flash_attention_kvcache_append(
+        k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin)
+    return new_seqlens, q_rot
+
+
+@torch.library.register_fake("flash_attention::kvcache_append")
+def flash_attention_kvcache_append_fake(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None,
+                                        rotary_cos=None, rotary_sin=None):
+    q_rot = k_cache.new_empty(0) if q is None else torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format), q_rot
+
+
+def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rotary_cos=None,
+                              rotary_sin=None):
+    """Append the new keys / values ``k`` / ``v`` [B, Hkv, Sn, D] to a KV cache IN PLACE, one HIP launch:
+    token i of sequence b is written at position ``n = cache_seqlens[b] + i`` -- row ``n % page_size`` of
+    page ``block_table[b, n // page_size]`` of the pools ``k_cache`` / ``v_cache`` [num_pages, Hkv,
+    page_size, D] (the layout ``flash_attn_paged_func`` reads), or, without a table, row n of batch row b of
+    a dense cache [B, Hkv, Smax, D] (the layout ``flash_attn_padded_func`` reads). With ``rotary_cos`` /
+    ``rotary_sin`` [max_pos, D] (``apply_rope``'s full-width rotate-half tables) k is rotated at position n
+    on the way, bit for bit as ``apply_rope`` would; v is stored as it is. Returns ``new_seqlens``
+    (int32 [B], a new tensor: ``min(cache_seqlens + Sn, capacity)``; ``cache_seqlens`` is not modified).
+
+    A write is DROPPED, never redirected: tokens past the capacity ``max_pages * page_size`` (``Smax``)
+    and tokens whose page id lies outside ``[0, num_pages)`` are not written -- unlike the read path,
+    which clamps ids, because a clamped write would corrupt another sequence's page. Negative lengths
+    count as 0; positions past the tables use their last row. Two sequences that write the same physical
+    row are the caller's error. The caches are never copied (any strides with a contiguous last dimension,
+    any alignment); no host synchronisation, so the call can be captured in a graph."""
+    return torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table, None,
+                                                    rotary_cos, rotary_sin)[0]
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
+                            cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
+                            return_seqlens=False):
+    """flash-attn's ``flash_attn_with_kvcache`` in this project's [B, H, S, D] layout: one serving step on
+    a paged (``block_table`` given) or dense KV cache. When ``k`` / ``v`` [B, Hkv, Sn, D] are given they are
+    appended in place at ``cache_seqlens`` (``flash_attn_kvcache_append``: the same drop rules); when the
+    rotary tables [max_pos, D] are given, k is rotated at its new positions and q [B, Hq, Sq, D] at the
+    sequence's last Sq positions after the append -- K, V and q in ONE launch. Then q attends over the
+    cache up to the advanced lengths: ``flash_attn_paged_func`` with a table, ``flash_attn_padded_func``
+    over ``[0, new_seqlens)`` without. Returns the attention output, or ``(out, new_seqlens)`` with
+    ``return_seqlens=True``; ``cache_seqlens`` (required, int32 [B]) is not modified -- the caller copies
+    ``new_seqlens`` into it (``cache_seqlens.copy_(new_seqlens)``) or takes them from
+    ``flash_attn_kvcache_append``. No host synchronisation (graph-capturable)."""
+    if cache_seqlens is None:
+        raise ValueError("flash_attn_with_kvcache needs cache_seqlens (int32 [batch])")
+    if (k is None) != (v is None):
+        raise ValueError("k and v must be given together")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("rotary_cos and rotary_sin must be given together")
+    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    new_seqlens, q_rot = cache_seqlens, q
+    if rotary_cos is not None:  # (cast as apply_rope casts its tables)
+        new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append(
+            k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos.to(q.dtype), rotary_sin.to(q.dtype))
+    elif k is not None:
+        new_seqlens, _ = torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table)
+    if block_table is not None:
+        out = flash_attn_paged_func(q_rot, k_cache, v_cache, block_table, new_seqlens, softmax_scale, causal)
+    else:
+        out = flash_attn_padded_func(q_rot, k_cache, v_cache, torch.zeros_like(new_seqlens), new_seqlens,
+                                     softmax_scale=softmax_scale, causal=causal)
+    return (out, new_seqlens) if return_seqlens else out
