@@ -340,36 +340,36 @@ int check_params(const fa_fwd_params *p, int dtype, int causal) {
     return FA_OK;
 }
 
-// head-dim dispatch: D <= 64 runs the 64-wide tile, 64 < D <= 128 the 128-wide tile (the reference
-// runs every D <= 128 on its 128 kernel, csrc/kernel_dispatcher.h:45-52)
-template <class DT, bool C>
-int launch(const fa_fwd_params &p, hipStream_t stream, const fa::PathArgs &xa = kNoPath) {
-    if (p.headdim <= 64)
-        return p.headdim == 64 ? launch_one<DT, C, 64, true>(p, xa, stream)
-                               : launch_one<DT, C, 64, false>(p, xa, stream);
-    return p.headdim == 128 ? launch_one<DT, C, 128, true>(p, xa, stream)
-                            : launch_one<DT, C, 128, false>(p, xa, stream);
+// the prefill / decode launch of the (dtype, causal, head-dim tile, exact head dim) instantiation
+int launch(const fa_fwd_params &p, int dtype, int causal, hipStream_t stream, const fa::PathArgs &xa = kNoPath) {
+    return fa::with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+        return fa::with_headdim(p.headdim, [&](auto d, auto exact) {
+            return launch_one<typename decltype(dt)::type, decltype(c)::value, decltype(d)::value,
+                              decltype(exact)::value>(p, xa, stream);
+        });
+    });
 }
-template <class DT, bool C>
-int launch_dec(const fa_fwd_params &p, const fa::DecArgs &a, void *ws, hipStream_t stream) {
-    if (p.headdim <= 64)
-        return p.headdim == 64 ? fa::launch_decode<DT, C, 64, true>(p, a, ws, stream)
-                               : fa::launch_decode<DT, C, 64, false>(p, a, ws, stream);
-    return p.headdim == 128 ? fa::launch_decode<DT, C, 128, true>(p, a, ws, stream)
-                            : fa::launch_decode<DT, C, 128, false>(p, a, ws, stream);
+int launch_dec(const fa_fwd_params &p, int dtype, int causal, const fa::DecArgs &a, void *ws,
+               hipStream_t stream) {
+    return fa::with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+        return fa::with_headdim(p.headdim, [&](auto d, auto exact) {
+            return fa::launch_decode<typename decltype(dt)::type, decltype(c)::value, decltype(d)::value,
+                                     decltype(exact)::value>(p, a, ws, stream);
+        });
+    });
 }
 
-// Split-KV decode path (fa_decode.hpp) for few (q-head, position) rows per (batch, kv-head): the
-// reference's Sq == 1 pack and short GQA query blocks. The `decode` knob (FA_GFX950_DECODE=0) sends
-// them to the prefill kernel instead (A/B measurements).
+// Split-KV decode path (fa_decode.hpp) where the decode rule (fa_launch.h decode_rule) holds.
 bool use_decode(const fa_fwd_params &p, const fa::PathArgs &ranges = kNoPath) {
-    if (ranges.q_rng) return false;  // query ranges: fa_fwd_w4
-    if (!fa::knobs().decode || fa::knobs().variant != 0) return false;
-    if (p.head_q_per_group * p.seqlen_q > fa::kDecMaxRows) return false;
-    // the row block's q rows are addressed by 32-bit offsets from the group's first q-head
-    const int64_t qspan = ((p.head_q_per_group - 1) * p.q_head_stride + (p.seqlen_q - 1) * p.q_seqlen_stride +
-                           p.headdim) * 2;
-    return qspan >= 0 && qspan < 0x7ff00000LL;
+    return fa::decode_rule(p) == fa::kDecOk && !ranges.q_rng;  // query ranges: fa_fwd_w4
+}
+
+// the params of a launch over absolute rows (packed varlen: sequence b is rows [cu[b], cu[b + 1]) of the
+// tensors; padded prefill: the row arrays of padded_rows): the batch strides are not used
+fa_fwd_params packed_params(const fa_fwd_params &base) {
+    fa_fwd_params p = base;
+    p.q_batch_stride = p.k_batch_stride = p.v_batch_stride = p.o_batch_stride = 0;
+    return p;
 }
 
 // ranges: per-sequence query / key ranges (fa_fwd_gfx950_padded), or kNoPath
@@ -387,9 +387,7 @@ int dispatch(const fa_fwd_params *params, int dtype, int causal, void *ws, int64
         if (ws && fa::decode_ws_bytes(p, a) > ws_bytes)
             return set_err(FA_ERR_INVALID_ARGUMENT, "workspace of %lld bytes is smaller than the %lld required",
                            (long long)ws_bytes, (long long)fa::decode_ws_bytes(p, a));
-        if (dtype == FA_DTYPE_F16)
-            return causal ? launch_dec<fa::F16, true>(p, a, ws, s) : launch_dec<fa::F16, false>(p, a, ws, s);
-        return causal ? launch_dec<fa::BF16, true>(p, a, ws, s) : launch_dec<fa::BF16, false>(p, a, ws, s);
+        return launch_dec(p, dtype, causal, a, ws, s);
     }
     fa::PathArgs xa = ranges;
     // key-split causal blocks (fa_launch.h use_split) when the workspace holds their partials; a
@@ -403,9 +401,7 @@ int dispatch(const fa_fwd_params *params, int dtype, int causal, void *ws, int64
             if (e != hipSuccess) return set_err(FA_ERR_LAUNCH, "hipMemsetAsync failed: %s", hipGetErrorString(e));
         }
     }
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch<fa::F16, true>(p, s, xa) : launch<fa::F16, false>(p, s, xa);
-    return causal ? launch<fa::BF16, true>(p, s, xa) : launch<fa::BF16, false>(p, s, xa);
+    return launch(p, dtype, causal, s, xa);
 }
 
 int check_varlen(const fa_varlen_params *v, int dtype, int causal) {
@@ -414,9 +410,7 @@ int check_varlen(const fa_varlen_params *v, int dtype, int causal) {
         return set_err(FA_ERR_INVALID_ARGUMENT, "cu_seqlens_q and cu_seqlens_k must be non-NULL");
     if (((uintptr_t)v->cu_seqlens_q & 3) || ((uintptr_t)v->cu_seqlens_k & 3))
         return set_err(FA_ERR_INVALID_ARGUMENT, "cu_seqlens must be 4-byte aligned int32 arrays");
-    // packed layout: the batch strides are not used (a sequence starts at row cu_seqlens[b])
-    fa_fwd_params p = v->base;
-    p.q_batch_stride = p.k_batch_stride = p.v_batch_stride = p.o_batch_stride = 0;
+    const fa_fwd_params p = packed_params(v->base);  // (a sequence starts at row cu_seqlens[b])
     return check_params(&p, dtype, causal);
 }
 
@@ -431,13 +425,8 @@ int dispatch_varlen(const fa_varlen_params *v, int dtype, int causal, void *stre
     if (window_left > 0x3fffffffLL) window_left = 0x3fffffff;  // (hides nothing either way)
     hipStream_t s = (hipStream_t)stream;
     const int *cq = v->cu_seqlens_q, *ck = v->cu_seqlens_k;
-    // packed rows: sequence b is rows [cu[b], cu[b + 1]) of the tensors, no batch offset
-    fa_fwd_params p = v->base;
-    p.q_batch_stride = p.k_batch_stride = p.v_batch_stride = p.o_batch_stride = 0;
     const fa::PathArgs xa{nullptr, nullptr, 0, 0, window_left < 0 ? -1 : (int)window_left, 1, cq, ck, nullptr, nullptr};
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch<fa::F16, true>(p, s, xa) : launch<fa::F16, false>(p, s, xa);
-    return causal ? launch<fa::BF16, true>(p, s, xa) : launch<fa::BF16, false>(p, s, xa);
+    return launch(packed_params(v->base), dtype, causal, s, xa);
 }
 
 int check_padded(const fa_padded_params *v, int dtype, int causal) {
@@ -514,16 +503,12 @@ int dispatch_padded(const fa_padded_params *v, int dtype, int causal, int64_t wi
     hipLaunchKernelGGL(padded_rows, dim3((uint32_t)((b.batch_size + 255) / 256)), dim3(256), 0, s, q_rng, k_rng,
                        v->q_start, v->q_end, v->k_start, v->k_end, (int)b.batch_size, q_rpb, k_rpb, (int)b.seqlen_q,
                        (int)b.seqlen_kv);
-    fa_fwd_params p = b;
-    p.q_batch_stride = p.k_batch_stride = p.v_batch_stride = p.o_batch_stride = 0;
     fa::PathArgs xa = kNoPath;
     xa.window_left = window_left < 0 ? -1 : (int)window_left;
     xa.rng_hi = (int)b.batch_size;
     xa.q_rng = q_rng;
     xa.k_rng = k_rng;
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch<fa::F16, true>(p, s, xa) : launch<fa::F16, false>(p, s, xa);
-    return causal ? launch<fa::BF16, true>(p, s, xa) : launch<fa::BF16, false>(p, s, xa);
+    return launch(packed_params(b), dtype, causal, s, xa);
 }
 
 int dispatch_rope(const fa_rope_fwd_params *r, int dtype, int causal, void *stream) {
@@ -539,10 +524,7 @@ int dispatch_rope(const fa_rope_fwd_params *r, int dtype, int causal, void *stre
     if (r->rope_seqlen_stride < 0 || r->rope_seqlen_stride * 2 * fa::kQoSpanRows + 256 > 0x7fffffffLL)
         return set_err(FA_ERR_UNSUPPORTED, "RoPE seqlen stride too large for 32-bit tile offsets");
     const fa::PathArgs ra{r->rope_cos, r->rope_sin, r->rope_batch_stride, r->rope_seqlen_stride, -1, 0, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch<fa::F16, true>(r->base, s, ra) : launch<fa::F16, false>(r->base, s, ra);
-    return causal ? launch<fa::BF16, true>(r->base, s, ra) : launch<fa::BF16, false>(r->base, s, ra);
+    return launch(r->base, dtype, causal, (hipStream_t)stream, ra);
 }
 
 // Local (sliding) window: keys below the first row's window are cut off the problem (views of k /
@@ -563,10 +545,7 @@ int dispatch_window(const fa_fwd_params *params, int dtype, int causal, int64_t 
     // the last query row's window starts at key Sk' - 1 - window_left: at or before 0, nothing is cut
     if (p.seqlen_kv - 1 <= window_left) return dispatch(&p, dtype, causal, nullptr, 0, stream);
     const fa::PathArgs xa{nullptr, nullptr, 0, 0, (int)window_left, 0, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch<fa::F16, true>(p, s, xa) : launch<fa::F16, false>(p, s, xa);
-    return causal ? launch<fa::BF16, true>(p, s, xa) : launch<fa::BF16, false>(p, s, xa);
+    return launch(p, dtype, causal, (hipStream_t)stream, xa);
 }
 
 }  // namespace

@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "fa_gfx950.h"
 
 namespace fa {
@@ -258,6 +260,19 @@ constexpr int kDecKeys = 32;  // keys per tile
 constexpr int kDecWaves = 4;  // waves per workgroup, each on its own contiguous key range
 // decode kernel when a (batch, kv-head) has at most this many (q-head, position) rows
 constexpr int kDecMaxRows = 2 * kDecRows;
+// The decode rule, for every dispatcher (the dense one falls back to the prefill kernel, the paged one
+// reports which part failed): few (q-head, position) rows per (batch, kv-head) -- the reference's
+// Sq == 1 pack and short GQA query blocks --, the `decode` knob on (FA_GFX950_DECODE=0 sends them to the
+// prefill kernel instead, A/B measurements) and the row block's q rows, addressed by 32-bit offsets
+// from the group's first q-head, inside that span.
+enum DecodeRule { kDecOk, kDecTooManyRows, kDecKnobOff, kDecQSpan };
+inline DecodeRule decode_rule(const fa_fwd_params &p) {
+    if (p.head_q_per_group * p.seqlen_q > kDecMaxRows) return kDecTooManyRows;
+    if (!knobs().decode || knobs().variant != 0) return kDecKnobOff;
+    const int64_t qspan = ((p.head_q_per_group - 1) * p.q_head_stride + (p.seqlen_q - 1) * p.q_seqlen_stride +
+                           p.headdim) * 2;
+    return qspan >= 0 && qspan < 0x7ff00000LL ? kDecOk : kDecQSpan;
+}
 // split plan: about kDecTargetWgs workgroups (the 128 KiB LDS ring admits one per CU), every wave
 // at least kDecMinTilesPerWave tiles. Fewer, longer splits than one per CU measured faster (B1 Hkv8
 // Sk131072 bf16: 5.2-5.5 TB/s at 160-192 workgroups vs 4.9-5.0 at 256, same run)
@@ -334,5 +349,29 @@ int launch_decode(const fa_fwd_params &p, DecArgs a, void *ws, hipStream_t strea
     extern template int launch_decode<DT, C, D, E>(const fa_fwd_params &, DecArgs, void *, hipStream_t);
 FA_FOR_EACH_INSTANCE(FA_DECLARE_EXTERN)
 #undef FA_DECLARE_EXTERN
+
+// Runtime -> compile-time dispatch over the instantiations, for every dispatcher's launch:
+//   with_dtype_causal(dtype, causal, [&](auto dt, auto c) { ... typename decltype(dt)::type, decltype(c)::value ... })
+//   with_headdim(headdim, [&](auto d, auto exact) { ... decltype(d)::value, decltype(exact)::value ... })
+// (F16 / BF16 are incomplete types: they travel as Tag<F16>)
+template <class T>
+struct Tag {
+    using type = T;
+};
+template <class F>
+inline int with_dtype_causal(int dtype, int causal, F &&f) {
+    if (dtype == FA_DTYPE_F16)
+        return causal ? f(Tag<F16>{}, std::true_type{}) : f(Tag<F16>{}, std::false_type{});
+    return causal ? f(Tag<BF16>{}, std::true_type{}) : f(Tag<BF16>{}, std::false_type{});
+}
+// head-dim dispatch: D <= 64 runs the 64-wide tile, 64 < D <= 128 the 128-wide tile (the reference
+// runs every D <= 128 on its 128 kernel, csrc/kernel_dispatcher.h:45-52); exact: D is the tile's width
+template <class F>
+inline int with_headdim(int64_t headdim, F &&f) {
+    using D64 = std::integral_constant<int, 64>;
+    using D128 = std::integral_constant<int, 128>;
+    if (headdim <= 64) return headdim == 64 ? f(D64{}, std::true_type{}) : f(D64{}, std::false_type{});
+    return headdim == 128 ? f(D128{}, std::true_type{}) : f(D128{}, std::false_type{});
+}
 
 }  // namespace fa

@@ -13,20 +13,21 @@
 namespace {
 using fa::set_err;
 
-// The decode rule of the dense dispatcher (use_decode): at most kDecMaxRows (q-head, position) rows per
-// (batch, kv-head), the decode knob on, the row block's q rows inside 32-bit offsets.
+// The decode rule (fa_launch.h decode_rule) is a requirement here: there is no other paged kernel.
 int check_decode_rule(const fa_fwd_params &p) {
-    if (p.head_q_per_group * p.seqlen_q > fa::kDecMaxRows)
+    switch (fa::decode_rule(p)) {
+    case fa::kDecTooManyRows:
         return set_err(FA_ERR_UNSUPPORTED,
                        "paged attention serves decode shapes only (the decode rule: head_q_per_group * seqlen_q "
                        "<= %d, got %lld): gather the pages and use fa_fwd_gfx950_padded",
                        fa::kDecMaxRows, (long long)(p.head_q_per_group * p.seqlen_q));
-    if (!fa::knobs().decode || fa::knobs().variant != 0)
+    case fa::kDecKnobOff:
         return set_err(FA_ERR_UNSUPPORTED, "paged attention needs the split-KV decode kernel (the decode knob is off)");
-    const int64_t qspan = ((p.head_q_per_group - 1) * p.q_head_stride + (p.seqlen_q - 1) * p.q_seqlen_stride +
-                           p.headdim) * 2;
-    if (qspan < 0 || qspan >= 0x7ff00000LL)
+    case fa::kDecQSpan:
         return set_err(FA_ERR_UNSUPPORTED, "q strides too large for the decode kernel's 32-bit row offsets");
+    case fa::kDecOk:
+        break;
+    }
     return FA_OK;
 }
 
@@ -66,13 +67,14 @@ fa::PagedDecArgs paged_plan(const fa_paged_params *v, bool split) {
     return a;
 }
 
-template <class DT, bool C>
-int launch_paged(const fa_fwd_params &p, const fa::PagedDecArgs &a, void *ws, hipStream_t stream) {
-    if (p.headdim <= 64)
-        return p.headdim == 64 ? fa::launch_decode_paged<DT, C, 64, true>(p, a, ws, stream)
-                               : fa::launch_decode_paged<DT, C, 64, false>(p, a, ws, stream);
-    return p.headdim == 128 ? fa::launch_decode_paged<DT, C, 128, true>(p, a, ws, stream)
-                            : fa::launch_decode_paged<DT, C, 128, false>(p, a, ws, stream);
+int launch_paged(const fa_fwd_params &p, int dtype, int causal, const fa::PagedDecArgs &a, void *ws,
+                 hipStream_t stream) {
+    return fa::with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+        return fa::with_headdim(p.headdim, [&](auto d, auto exact) {
+            return fa::launch_decode_paged<typename decltype(dt)::type, decltype(c)::value, decltype(d)::value,
+                                           decltype(exact)::value>(p, a, ws, stream);
+        });
+    });
 }
 }  // namespace
 
@@ -87,10 +89,7 @@ extern "C" int fa_fwd_gfx950_paged(const fa_paged_params *params, int dtype, int
     if (workspace && fa::decode_ws_bytes(p, a) > workspace_bytes)
         return set_err(FA_ERR_INVALID_ARGUMENT, "workspace of %lld bytes is smaller than the %lld required",
                        (long long)workspace_bytes, (long long)fa::decode_ws_bytes(p, a));
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == FA_DTYPE_F16)
-        return causal ? launch_paged<fa::F16, true>(p, a, workspace, s) : launch_paged<fa::F16, false>(p, a, workspace, s);
-    return causal ? launch_paged<fa::BF16, true>(p, a, workspace, s) : launch_paged<fa::BF16, false>(p, a, workspace, s);
+    return launch_paged(p, dtype, causal, a, workspace, (hipStream_t)stream);
 }
 
 extern "C" int64_t fa_fwd_gfx950_paged_workspace_size(const fa_paged_params *params, int dtype, int causal) {

@@ -10,6 +10,9 @@
 //     RuntimeError instead of exit() (reference csrc/utils.h:9-18);
 //   * inputs whose base pointer or strides are not 16-byte aligned (the reference silently assumes
 //     alignment, csrc/flash_attention_template.cuh:135-137) are copied to a contiguous buffer.
+//
+// Every entry point reads: its checks, its layout decisions, one fill_params call, the fields where its
+// layout deviates from the dense 4-D one, its call. The steps they share are named once, below.
 #include <torch/extension.h>
 
 #include <c10/core/DeviceGuard.h>
@@ -46,6 +49,19 @@ bool device_is_gfx950(int device) {
     return cache[device] == 1;
 }
 
+void require_gfx950(const torch::Device &device) {
+    TORCH_CHECK(device_is_gfx950(device.index()),
+                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+}
+
+int fa_dtype(const torch::Tensor &t) { return t.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16; }
+
+void *current_stream(const torch::Tensor &t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
+
+void check_rc(int rc, const char *fn) {
+    TORCH_CHECK(rc == FA_OK, fn, " failed (code ", rc, "): ", fa_last_error());
+}
+
 bool aligned16(const torch::Tensor &t) {
     if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 != 0) return false;
     for (int i = 0; i < 3; ++i)
@@ -53,9 +69,99 @@ bool aligned16(const torch::Tensor &t) {
     return true;
 }
 
+torch::Tensor aligned_or_contiguous(const torch::Tensor &t) { return aligned16(t) ? t : t.contiguous(); }
+
+// stride-preserving output (reference :85): o inherits q's physical layout, so the
+// transpose(1, 2).reshape(...) of the HF attention caller stays copy-free
+torch::Tensor alloc_out_like(const torch::Tensor &qx) {
+    auto o = torch::empty_like(qx);
+    return aligned16(o) ? o : torch::empty(qx.sizes(), qx.options());
+}
+
+// the kernels' fp32 scratch: taken from torch's caching allocator on the current stream, so it is
+// graph-capture safe and reused; undefined (data: nullptr) when the launch needs none
+torch::Tensor workspace_for(int64_t bytes, const torch::TensorOptions &options) {
+    return bytes > 0 ? torch::empty({bytes}, options.dtype(torch::kUInt8)) : torch::Tensor();
+}
+void *data_or_null(const torch::Tensor &ws) { return ws.defined() ? ws.data_ptr() : nullptr; }
+
+// o (of the packed or copied q) in the caller's shape
+torch::Tensor shaped_like(const torch::Tensor &o, const torch::Tensor &q) {
+    return o.sizes() != q.sizes() ? o.reshape(q.sizes()) : o;
+}
+
 int64_t stride_or_zero(const torch::Tensor &t, int dim) {
     // a size-1 dimension may carry any stride; the kernel never steps along it
     return t.size(dim) == 1 ? 0 : t.stride(dim);
+}
+
+// The checks every dense entry words the same way (reference :21-27, :39-43, :53-59), in three pieces
+// because the entries put checks of their own between them.
+void check_4d(const torch::Tensor &q, const torch::Tensor &k, const torch::Tensor &v) {
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D [batch, heads, seqlen, dim]");
+}
+void check_qkv_4d(const torch::Tensor &q, const torch::Tensor &k, const torch::Tensor &v) {
+    check_4d(q, k, v);
+    TORCH_CHECK(q.size(0) == k.size(0) && q.size(0) == v.size(0), "q, k, v must have the same batch size");
+    TORCH_CHECK(k.size(1) == v.size(1), "k, v must have the same number of heads");
+    TORCH_CHECK(k.size(2) == v.size(2), "k, v must have the same sequence length");
+    TORCH_CHECK(q.size(3) == k.size(3) && q.size(3) == v.size(3), "q, k, v must have the same hidden dimension");
+}
+void check_dtype(const torch::Tensor &q, const torch::Tensor &k, const torch::Tensor &v) {
+    TORCH_CHECK(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "q, k, v must have the same data type");
+    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
+                "q, k, v only support fp16 or bf16 data type");
+}
+// kernel constraints on the head dim (q's last dimension) and the device; the last check an entry
+// can fail on CPU tensors
+void check_headdim_device(const torch::Tensor &q, const torch::Tensor &k, const torch::Tensor &v) {
+    TORCH_CHECK(q.size(-1) % 8 == 0, "hidden dimension must be multiple of 8");
+    TORCH_CHECK(q.size(-1) <= 128, "only support hidden dimension <= 128");
+    TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q, k, v must be on CUDA device");
+    TORCH_CHECK(q.device() == k.device() && q.device() == v.device(), "q, k, v must be on the same CUDA device");
+}
+
+// Decode q-head packing (reference :64-83): with one query row per head, the q-heads of one
+// kv group become the rows of a single (batch, kv-head) problem so one workgroup serves the
+// whole group from one K/V stream: q [B, Hq, 1, D] as [B, Hkv, g, D], which fill_params describes as
+// MHA over the packed rows (reference :100). The caller drops causal masking, as the reference (:81).
+torch::Tensor pack_head_q(const torch::Tensor &qx, int64_t head_kv) {
+    torch::Tensor p = qx.reshape({qx.size(0), head_kv, qx.size(1) / head_kv, qx.size(3)});
+    return aligned16(p) ? p : p.contiguous();
+}
+
+// The dense 4-D problem of q [B, Hq, Sq, D], k / v [B, Hkv, Sk, D] and o (q's shape): pointers, sizes,
+// the three stride groups and the scale. An entry whose layout differs overwrites those fields after
+// the call.
+void fill_params(fa_fwd_params &params, const torch::Tensor &qx, const torch::Tensor &kx, const torch::Tensor &vx,
+                 const torch::Tensor &o, float softmax_scale) {
+    params.q_ptr = qx.data_ptr();
+    params.k_ptr = kx.data_ptr();
+    params.v_ptr = vx.data_ptr();
+    params.o_ptr = o.data_ptr();
+    params.batch_size = qx.size(0);
+    params.num_heads_q = qx.size(1);
+    params.num_heads_kv = kx.size(1);
+    params.seqlen_q = qx.size(2);
+    params.seqlen_kv = kx.size(2);
+    params.headdim = qx.size(3);
+    params.head_q_per_group = qx.size(1) / kx.size(1);
+    params.q_batch_stride = stride_or_zero(qx, 0);
+    params.k_batch_stride = stride_or_zero(kx, 0);
+    params.v_batch_stride = stride_or_zero(vx, 0);
+    params.o_batch_stride = stride_or_zero(o, 0);
+    params.q_head_stride = stride_or_zero(qx, 1);
+    params.k_head_stride = stride_or_zero(kx, 1);
+    params.v_head_stride = stride_or_zero(vx, 1);
+    params.o_head_stride = stride_or_zero(o, 1);
+    params.q_seqlen_stride = stride_or_zero(qx, 2);
+    params.k_seqlen_stride = stride_or_zero(kx, 2);
+    params.v_seqlen_stride = stride_or_zero(vx, 2);
+    params.o_seqlen_stride = stride_or_zero(o, 2);
+    // log2(e) folded into the scale on the host (reference :87)
+    // (float * double -> float, exactly as `softmax_scale *= M_LOG2E` there)
+    softmax_scale *= M_LOG2E;
+    params.softmax_scale = softmax_scale;
 }
 
 // cos / sin tables of RoPE: [B, S, D], [1, S, D] or [S, D] of x's dtype on x's device; returns the
@@ -90,7 +196,7 @@ fa_rope_params rope_params(const torch::Tensor &x, const torch::Tensor &out, con
     r.out_batch_stride = out.stride(0);
     r.out_head_stride = out.stride(1);
     r.out_seqlen_stride = out.stride(2);
-    r.cs_batch_stride = cs.size(0) == 1 ? 0 : cs.stride(0);
+    r.cs_batch_stride = stride_or_zero(cs, 0);
     r.cs_seqlen_stride = cs.stride(1);
     return r;
 }
@@ -112,9 +218,7 @@ torch::Tensor rope_apply(torch::Tensor &x, torch::Tensor &cos, torch::Tensor &si
     auto out = torch::empty_like(x);
     if (x.numel() == 0) return out;
     const fa_rope_params r = rope_params(x, out, cs, sn);
-    const int dtype = x.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    const int rc = fa_rope_gfx950(&r, dtype, c10::hip::getCurrentHIPStream(x.device().index()).stream());
-    TORCH_CHECK(rc == FA_OK, "fa_rope_gfx950 failed (code ", rc, "): ", fa_last_error());
+    check_rc(fa_rope_gfx950(&r, fa_dtype(x), current_stream(x)), "fa_rope_gfx950");
     return out;
 }
 
@@ -122,11 +226,7 @@ torch::Tensor rope_apply(torch::Tensor &x, torch::Tensor &cos, torch::Tensor &si
 torch::Tensor fwd_impl(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, float softmax_scale, bool causal,
                        int64_t window_left) {
     // Check input shape (reference :21-37)
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D [batch, heads, seqlen, dim]");
-    TORCH_CHECK(q.size(0) == k.size(0) && q.size(0) == v.size(0), "q, k, v must have the same batch size");
-    TORCH_CHECK(k.size(1) == v.size(1), "k, v must have the same number of heads");
-    TORCH_CHECK(k.size(2) == v.size(2), "k, v must have the same sequence length");
-    TORCH_CHECK(q.size(3) == k.size(3) && q.size(3) == v.size(3), "q, k, v must have the same hidden dimension");
+    check_qkv_4d(q, k, v);
     TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0,
                 "q, k, v must have at least one element");
     TORCH_CHECK(k.size(2) > 0, "q, k, v must have at least one element");
@@ -135,9 +235,7 @@ torch::Tensor fwd_impl(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, flo
     TORCH_CHECK(q.size(1) % k.size(1) == 0, "number of heads in q must be multiple of number of heads in k and v");
 
     // Check input data type (reference :39-43)
-    TORCH_CHECK(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "q, k, v must have the same data type");
-    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
-                "q, k, v only support fp16 or bf16 data type");
+    check_dtype(q, k, v);
 
     // Check input memory contiguity (reference :45-51)
     TORCH_CHECK(q.stride(3) == 1, "q must be contiguous in the last dimension");
@@ -145,99 +243,35 @@ torch::Tensor fwd_impl(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, flo
     TORCH_CHECK(v.stride(3) == 1, "v must be contiguous in the last dimension");
 
     // Check kernel constraints (reference :53-59)
-    TORCH_CHECK(q.size(3) % 8 == 0, "hidden dimension must be multiple of 8");
-    TORCH_CHECK(q.size(3) <= 128, "only support hidden dimension <= 128");
-    TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q, k, v must be on CUDA device");
-    TORCH_CHECK(q.device() == k.device() && q.device() == v.device(), "q, k, v must be on the same CUDA device");
+    check_headdim_device(q, k, v);
 
     c10::DeviceGuard device_guard(q.device());
-    TORCH_CHECK(device_is_gfx950(q.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(q.device());
 
-    torch::Tensor qx = aligned16(q) ? q : q.contiguous();
-    torch::Tensor kx = aligned16(k) ? k : k.contiguous();
-    torch::Tensor vx = aligned16(v) ? v : v.contiguous();
-
-    int64_t bs = qx.size(0);
-    int64_t head_q = qx.size(1);
-    const int64_t head_kv = kx.size(1);
-    int64_t seqlen_q = qx.size(2);
-    const int64_t seqlen_kv = kx.size(2);
-    const int64_t headdim = qx.size(3);
-    const int64_t head_q_per_group = head_q / head_kv;
-
-    // Decode q-head packing (reference :64-83): with one query row per head, the q-heads of one
-    // kv group become the rows of a single (batch, kv-head) problem so one workgroup serves the
-    // whole group from one K/V stream. Causal masking is dropped, as in the reference (:81).
-    const bool is_pack_head_q = seqlen_q == 1 && window_left < 0;
-    if (is_pack_head_q) {
-        head_q = head_kv;
-        seqlen_q = seqlen_q * head_q_per_group;
+    torch::Tensor qx = aligned_or_contiguous(q);
+    torch::Tensor kx = aligned_or_contiguous(k);
+    torch::Tensor vx = aligned_or_contiguous(v);
+    if (qx.size(2) == 1 && window_left < 0) {  // (the window entry never packs)
+        qx = pack_head_q(qx, kx.size(1));
         causal = false;
-        qx = qx.reshape({bs, head_q, seqlen_q, headdim});
-        if (!aligned16(qx)) qx = qx.contiguous();
     }
-
-    // stride-preserving output (reference :85): o inherits q's physical layout, so the
-    // transpose(1, 2).reshape(...) of the HF attention caller stays copy-free
-    auto o = torch::empty_like(qx);
-    if (!aligned16(o)) o = torch::empty(qx.sizes(), qx.options());
+    auto o = alloc_out_like(qx);
 
     fa_fwd_params params;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = bs;
-    params.num_heads_q = head_q;
-    params.num_heads_kv = head_kv;
-    params.seqlen_q = seqlen_q;
-    params.seqlen_kv = seqlen_kv;
-    params.headdim = headdim;
-    // pack path runs as MHA over the packed rows (reference :100)
-    params.head_q_per_group = is_pack_head_q ? 1 : head_q_per_group;
-    params.q_batch_stride = stride_or_zero(qx, 0);
-    params.k_batch_stride = stride_or_zero(kx, 0);
-    params.v_batch_stride = stride_or_zero(vx, 0);
-    params.o_batch_stride = stride_or_zero(o, 0);
-    params.q_head_stride = stride_or_zero(qx, 1);
-    params.k_head_stride = stride_or_zero(kx, 1);
-    params.v_head_stride = stride_or_zero(vx, 1);
-    params.o_head_stride = stride_or_zero(o, 1);
-    params.q_seqlen_stride = stride_or_zero(qx, 2);
-    params.k_seqlen_stride = stride_or_zero(kx, 2);
-    params.v_seqlen_stride = stride_or_zero(vx, 2);
-    params.o_seqlen_stride = stride_or_zero(o, 2);
-    // log2(e) folded into the scale on the host (reference :87)
-    // (float * double -> float, exactly as `softmax_scale *= M_LOG2E` there)
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
+    fill_params(params, qx, kx, vx, o, softmax_scale);
 
-    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    void *stream = c10::hip::getCurrentHIPStream(qx.device().index()).stream();
+    const int dtype = fa_dtype(qx);
+    void *stream = current_stream(qx);
     if (window_left >= 0) {
-        const int rc = fa_fwd_gfx950_window(&params, dtype, causal ? 1 : 0, window_left, stream);
-        TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_window failed (code ", rc, "): ", fa_last_error());
-        if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
-        return o;
+        check_rc(fa_fwd_gfx950_window(&params, dtype, causal ? 1 : 0, window_left, stream), "fa_fwd_gfx950_window");
+        return shaped_like(o, q);
     }
-    // split-KV decode (few rows per kv-head) wants fp32 scratch for its partials: taken from
-    // torch's caching allocator on the current stream, so it is graph-capture safe and reused
+    // split-KV decode (few rows per kv-head) and key-split causal blocks want fp32 scratch for their partials
     const int64_t ws_bytes = fa_fwd_gfx950_workspace_size(&params, dtype, causal ? 1 : 0);
     TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws;
-    if (ws_bytes > 0) ws = torch::empty({ws_bytes}, qx.options().dtype(torch::kUInt8));
-    const int rc = fa_fwd_gfx950_ws(&params, dtype, causal ? 1 : 0, ws_bytes > 0 ? ws.data_ptr() : nullptr,
-                                    ws_bytes, stream);
-    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_ws failed (code ", rc, "): ", fa_last_error());
-
-    if (is_pack_head_q) {
-        head_q = head_kv * head_q_per_group;
-        seqlen_q = seqlen_q / head_q_per_group;
-        o = o.reshape({bs, head_q, seqlen_q, headdim});
-    }
-    if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
-    return o;
+    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+    check_rc(fa_fwd_gfx950_ws(&params, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, stream), "fa_fwd_gfx950_ws");
+    return shaped_like(o, q);
 }
 
 torch::Tensor flash_attention_fwd(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, float softmax_scale,
@@ -252,7 +286,7 @@ torch::Tensor flash_attention_fwd(torch::Tensor &q, torch::Tensor &k, torch::Ten
 torch::Tensor flash_attention_window_fwd(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, int64_t window_left,
                                          float softmax_scale, bool causal) {
     TORCH_CHECK(window_left >= 0, "window_left must be >= 0");
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D [batch, heads, seqlen, dim]");
+    check_4d(q, k, v);
     TORCH_CHECK(k.size(2) == v.size(2), "k, v must have the same sequence length");
     const int64_t sq = q.size(2), sk = k.size(2);
     const int64_t cut = sk - sq - window_left;
@@ -267,7 +301,7 @@ torch::Tensor flash_attention_window_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // dims rotate q with rope_apply first and take the plain path.
 torch::Tensor flash_attention_rope_fwd(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, torch::Tensor &cos,
                                        torch::Tensor &sin, float softmax_scale, bool causal) {
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D [batch, heads, seqlen, dim]");
+    check_4d(q, k, v);
     TORCH_CHECK(k.size(1) > 0 && q.size(1) % k.size(1) == 0,
                 "number of heads in q must be multiple of number of heads in k and v");
     const int64_t g = q.size(1) / k.size(1), sq = q.size(2), d = q.size(3);
@@ -278,64 +312,31 @@ torch::Tensor flash_attention_rope_fwd(torch::Tensor &q, torch::Tensor &k, torch
         return flash_attention_fwd(qr, k, v, softmax_scale, causal);
     }
     // the checks of flash_attention_fwd on a dry run of the same tensors (no Sq == 1 pack here)
-    TORCH_CHECK(q.size(0) == k.size(0) && q.size(0) == v.size(0), "q, k, v must have the same batch size");
-    TORCH_CHECK(k.size(1) == v.size(1), "k, v must have the same number of heads");
-    TORCH_CHECK(k.size(2) == v.size(2), "k, v must have the same sequence length");
-    TORCH_CHECK(q.size(3) == k.size(3) && q.size(3) == v.size(3), "q, k, v must have the same hidden dimension");
+    check_qkv_4d(q, k, v);
     TORCH_CHECK(k.size(2) > 0 && q.size(0) > 0, "q, k, v must have at least one element");
     TORCH_CHECK(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "q, k, v must have the same data type");
     TORCH_CHECK(k.stride(3) == 1 && v.stride(3) == 1, "k, v must be contiguous in the last dimension");
     TORCH_CHECK(k.is_cuda() && v.is_cuda() && q.device() == k.device() && q.device() == v.device(),
                 "q, k, v must be on the same CUDA device");
     c10::DeviceGuard device_guard(q.device());
-    TORCH_CHECK(device_is_gfx950(q.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(q.device());
     torch::Tensor cs = rope_table(cos, q, q.size(0), sq, d, "cos");
     torch::Tensor sn = rope_table(sin, q, q.size(0), sq, d, "sin");
     TORCH_CHECK(cs.size(0) == sn.size(0) && cs.strides() == sn.strides(), "cos and sin must have the same layout");
-    torch::Tensor qx = aligned16(q) ? q : q.contiguous();
-    torch::Tensor kx = aligned16(k) ? k : k.contiguous();
-    torch::Tensor vx = aligned16(v) ? v : v.contiguous();
-    auto o = torch::empty_like(qx);
-    if (!aligned16(o)) o = torch::empty(qx.sizes(), qx.options());
+    torch::Tensor qx = aligned_or_contiguous(q);
+    torch::Tensor kx = aligned_or_contiguous(k);
+    torch::Tensor vx = aligned_or_contiguous(v);
+    auto o = alloc_out_like(qx);
 
     fa_rope_fwd_params rp;
-    fa_fwd_params &params = rp.base;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = qx.size(0);
-    params.num_heads_q = qx.size(1);
-    params.num_heads_kv = kx.size(1);
-    params.seqlen_q = sq;
-    params.seqlen_kv = kx.size(2);
-    params.headdim = d;
-    params.head_q_per_group = g;
-    params.q_batch_stride = stride_or_zero(qx, 0);
-    params.k_batch_stride = stride_or_zero(kx, 0);
-    params.v_batch_stride = stride_or_zero(vx, 0);
-    params.o_batch_stride = stride_or_zero(o, 0);
-    params.q_head_stride = stride_or_zero(qx, 1);
-    params.k_head_stride = stride_or_zero(kx, 1);
-    params.v_head_stride = stride_or_zero(vx, 1);
-    params.o_head_stride = stride_or_zero(o, 1);
-    params.q_seqlen_stride = stride_or_zero(qx, 2);
-    params.k_seqlen_stride = stride_or_zero(kx, 2);
-    params.v_seqlen_stride = stride_or_zero(vx, 2);
-    params.o_seqlen_stride = stride_or_zero(o, 2);
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
-    rp.rope_cos = cs.data_ptr();
-    rp.rope_sin = sn.data_ptr();
-    rp.rope_batch_stride = cs.size(0) == 1 ? 0 : cs.stride(0);
-    rp.rope_seqlen_stride = cs.stride(1);
-    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    const int rc = fa_fwd_gfx950_rope(&rp, dtype, causal ? 1 : 0,
-                                      c10::hip::getCurrentHIPStream(qx.device().index()).stream());
-    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_rope failed (code ", rc, "): ", fa_last_error());
-    if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
-    return o;
+    fill_params(rp.base, qx, kx, vx, o, softmax_scale);
+    const fa_rope_params tables = rope_params(qx, o, cs, sn);  // the tables as rope_apply describes them
+    rp.rope_cos = tables.cos;
+    rp.rope_sin = tables.sin;
+    rp.rope_batch_stride = tables.cs_batch_stride;
+    rp.rope_seqlen_stride = tables.cs_seqlen_stride;
+    check_rc(fa_fwd_gfx950_rope(&rp, fa_dtype(qx), causal ? 1 : 0, current_stream(qx)), "fa_fwd_gfx950_rope");
+    return shaped_like(o, q);
 }
 
 // Variable-length (packed) batches: q [total_q, Hq, D], k / v [total_k, Hkv, D], cu_seqlens_* int32
@@ -351,15 +352,10 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     TORCH_CHECK(q.size(2) == k.size(2) && q.size(2) == v.size(2), "q, k, v must have the same hidden dimension");
     TORCH_CHECK(q.size(1) > 0 && k.size(1) > 0 && q.size(2) > 0, "q, k, v must have at least one head");
     TORCH_CHECK(q.size(1) % k.size(1) == 0, "number of heads in q must be multiple of number of heads in k and v");
-    TORCH_CHECK(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "q, k, v must have the same data type");
-    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
-                "q, k, v only support fp16 or bf16 data type");
+    check_dtype(q, k, v);
     TORCH_CHECK(q.stride(2) == 1 && k.stride(2) == 1 && v.stride(2) == 1,
                 "q, k, v must be contiguous in the last dimension");
-    TORCH_CHECK(q.size(2) % 8 == 0, "hidden dimension must be multiple of 8");
-    TORCH_CHECK(q.size(2) <= 128, "only support hidden dimension <= 128");
-    TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q, k, v must be on CUDA device");
-    TORCH_CHECK(q.device() == k.device() && q.device() == v.device(), "q, k, v must be on the same CUDA device");
+    check_headdim_device(q, k, v);
     TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32 && cu_seqlens_k.dtype() == torch::kInt32,
                 "cu_seqlens must be int32");
     TORCH_CHECK(cu_seqlens_q.dim() == 1 && cu_seqlens_k.dim() == 1 && cu_seqlens_q.size(0) == cu_seqlens_k.size(0) &&
@@ -370,8 +366,7 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     TORCH_CHECK(max_seqlen_q >= 0 && max_seqlen_k >= 0, "max_seqlen must be non-negative");
 
     c10::DeviceGuard device_guard(q.device());
-    TORCH_CHECK(device_is_gfx950(q.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(q.device());
     auto o = torch::empty_like(q);
     if (q.size(0) == 0 || max_seqlen_q == 0) return o;
     if (max_seqlen_k == 0) return o.zero_();  // no sequence has a key: every row is 0
@@ -386,7 +381,9 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     if (!aligned_rows(o)) o = torch::empty(q.sizes(), q.options());
     torch::Tensor cq = cu_seqlens_q.contiguous(), ck = cu_seqlens_k.contiguous();
 
-    fa_varlen_params vp;
+    // the packed 3-D layout, not fill_params' dense one: rows are dimension 0, the strides are taken as
+    // they are, and the four batch strides stay 0 (a sequence starts at row cu_seqlens[b])
+    fa_varlen_params vp = {};
     fa_fwd_params &params = vp.base;
     params.q_ptr = qx.data_ptr();
     params.k_ptr = kx.data_ptr();
@@ -399,7 +396,6 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     params.seqlen_kv = max_seqlen_k;
     params.headdim = qx.size(2);
     params.head_q_per_group = qx.size(1) / kx.size(1);
-    params.q_batch_stride = params.k_batch_stride = params.v_batch_stride = params.o_batch_stride = 0;
     params.q_head_stride = qx.stride(1);
     params.k_head_stride = kx.stride(1);
     params.v_head_stride = vx.stride(1);
@@ -413,11 +409,11 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     vp.cu_seqlens_q = cq.data_ptr<int32_t>();
     vp.cu_seqlens_k = ck.data_ptr<int32_t>();
 
-    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    void *stream = c10::hip::getCurrentHIPStream(qx.device().index()).stream();
+    const int dtype = fa_dtype(qx);
+    void *stream = current_stream(qx);
     const int rc = window_left >= 0 ? fa_fwd_gfx950_varlen_window(&vp, dtype, causal ? 1 : 0, window_left, stream)
                                     : fa_fwd_gfx950_varlen(&vp, dtype, causal ? 1 : 0, stream);
-    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_varlen failed (code ", rc, "): ", fa_last_error());
+    check_rc(rc, "fa_fwd_gfx950_varlen");
     return o;
 }
 
@@ -432,23 +428,14 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
                                          c10::optional<torch::Tensor> q_start, c10::optional<torch::Tensor> q_end,
                                          torch::Tensor &k_start, torch::Tensor &k_end, float softmax_scale,
                                          bool causal, int64_t window_left) {
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D [batch, heads, seqlen, dim]");
-    TORCH_CHECK(q.size(0) == k.size(0) && q.size(0) == v.size(0), "q, k, v must have the same batch size");
-    TORCH_CHECK(k.size(1) == v.size(1), "k, v must have the same number of heads");
-    TORCH_CHECK(k.size(2) == v.size(2), "k, v must have the same sequence length");
-    TORCH_CHECK(q.size(3) == k.size(3) && q.size(3) == v.size(3), "q, k, v must have the same hidden dimension");
+    check_qkv_4d(q, k, v);
     TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0 && k.size(2) > 0,
                 "q, k, v must have at least one element");
     TORCH_CHECK(q.size(1) % k.size(1) == 0, "number of heads in q must be multiple of number of heads in k and v");
-    TORCH_CHECK(q.dtype() == k.dtype() && q.dtype() == v.dtype(), "q, k, v must have the same data type");
-    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
-                "q, k, v only support fp16 or bf16 data type");
+    check_dtype(q, k, v);
     TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1,
                 "q, k, v must be contiguous in the last dimension");
-    TORCH_CHECK(q.size(3) % 8 == 0, "hidden dimension must be multiple of 8");
-    TORCH_CHECK(q.size(3) <= 128, "only support hidden dimension <= 128");
-    TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q, k, v must be on CUDA device");
-    TORCH_CHECK(q.device() == k.device() && q.device() == v.device(), "q, k, v must be on the same CUDA device");
+    check_headdim_device(q, k, v);
     TORCH_CHECK(q_start.has_value() == q_end.has_value(), "q_start and q_end must be given together");
     const int64_t bs = q.size(0);
     auto check_range = [&](const torch::Tensor &t, const char *name) {
@@ -463,8 +450,7 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
         check_range(*q_end, "q_end");
     }
     c10::DeviceGuard device_guard(q.device());
-    TORCH_CHECK(device_is_gfx950(q.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(q.device());
 
     // the prefill kernel addresses a ranged sequence by absolute rows (row r at base + r * seqlen
     // stride): the batch stride must be a multiple of the seqlen stride, the same multiple for k and v
@@ -474,33 +460,28 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
         if (t.stride(2) <= 0 || t.stride(0) % t.stride(2) != 0) return -1;
         return t.stride(0) / t.stride(2);
     };
-    torch::Tensor qx = aligned16(q) ? q : q.contiguous();
-    torch::Tensor kx = aligned16(k) ? k : k.contiguous();
-    torch::Tensor vx = aligned16(v) ? v : v.contiguous();
+    torch::Tensor qx = aligned_or_contiguous(q);
+    torch::Tensor kx = aligned_or_contiguous(k);
+    torch::Tensor vx = aligned_or_contiguous(v);
     if (rows_per_batch(kx) < 0 || rows_per_batch(kx) != rows_per_batch(vx) || kx.stride(2) != vx.stride(2)) {
         kx = kx.contiguous();
         vx = vx.contiguous();
     }
-    int64_t head_q = qx.size(1), seqlen_q = qx.size(2);
-    const int64_t head_kv = kx.size(1), headdim = qx.size(3), g = head_q / head_kv;
     torch::Tensor ks = k_start.contiguous(), ke = k_end.contiguous(), qs, qe;
     if (q_ranges) {
         qs = q_start->contiguous();
         qe = q_end->contiguous();
     }
     // decode: one query row that sees the last window_left + 1 keys of its range -> narrow the range
-    if (window_left >= 0 && seqlen_q == 1 && !q_ranges) {
+    if (window_left >= 0 && qx.size(2) == 1 && !q_ranges) {
         ks = torch::maximum(ks, ke - (int32_t)std::min<int64_t>(window_left + 1, 0x7fffffff));
         window_left = -1;
     }
     // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
-    const bool pack = seqlen_q == 1 && !q_ranges && window_left < 0;
+    const bool pack = qx.size(2) == 1 && !q_ranges && window_left < 0;
     if (pack) {
-        head_q = head_kv;
-        seqlen_q = g;
+        qx = pack_head_q(qx, kx.size(1));
         causal = false;
-        qx = qx.reshape({bs, head_q, seqlen_q, headdim});
-        if (!aligned16(qx)) qx = qx.contiguous();
     }
     if (rows_per_batch(qx) < 0) qx = qx.contiguous();  // (the prefill path may run, also after a pack)
     auto o = torch::empty_like(qx);
@@ -516,48 +497,27 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 
     fa_padded_params pp;
     fa_fwd_params &params = pp.base;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = bs;
-    params.num_heads_q = head_q;
-    params.num_heads_kv = head_kv;
-    params.seqlen_q = seqlen_q;
-    params.seqlen_kv = kx.size(2);
-    params.headdim = headdim;
-    params.head_q_per_group = pack ? 1 : g;
-    params.q_batch_stride = stride_or_zero(qx, 0);
-    params.k_batch_stride = stride_or_zero(kx, 0);
-    params.v_batch_stride = stride_or_zero(vx, 0);
-    params.o_batch_stride = stride_or_zero(o, 0);
-    params.q_head_stride = stride_or_zero(qx, 1);
-    params.k_head_stride = stride_or_zero(kx, 1);
-    params.v_head_stride = stride_or_zero(vx, 1);
-    params.o_head_stride = stride_or_zero(o, 1);
+    fill_params(params, qx, kx, vx, o, softmax_scale);
     // the seqlen strides convert rows into addresses on the prefill path, even at size 1
-    params.q_seqlen_stride = pack ? stride_or_zero(qx, 2) : qx.stride(2);
+    if (!pack) {
+        params.q_seqlen_stride = qx.stride(2);
+        params.o_seqlen_stride = o.stride(2);
+    }
     params.k_seqlen_stride = kx.stride(2);
     params.v_seqlen_stride = vx.stride(2);
-    params.o_seqlen_stride = pack ? stride_or_zero(o, 2) : o.stride(2);
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
     pp.q_start = q_ranges ? qs.data_ptr<int32_t>() : nullptr;
     pp.q_end = q_ranges ? qe.data_ptr<int32_t>() : nullptr;
     pp.k_start = ks.data_ptr<int32_t>();
     pp.k_end = ke.data_ptr<int32_t>();
 
-    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    void *stream = c10::hip::getCurrentHIPStream(qx.device().index()).stream();
+    const int dtype = fa_dtype(qx);
     const int64_t ws_bytes = fa_fwd_gfx950_padded_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
     TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_padded_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws;
-    if (ws_bytes > 0) ws = torch::empty({ws_bytes}, qx.options().dtype(torch::kUInt8));
-    const int rc = fa_fwd_gfx950_padded(&pp, dtype, causal ? 1 : 0, window_left,
-                                        ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, stream);
-    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_padded failed (code ", rc, "): ", fa_last_error());
-    if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
-    return o;
+    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+    check_rc(fa_fwd_gfx950_padded(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
+                                  current_stream(qx)),
+             "fa_fwd_gfx950_padded");
+    return shaped_like(o, q);
 }
 
 // Paged KV-cache decode (include/fa_gfx950_paged.h fa_fwd_gfx950_paged): q [B, Hq, Sq, D] dense, the
@@ -578,16 +538,10 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
                 "number of heads in q must be multiple of number of heads in k and v");
     TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
-    TORCH_CHECK(q.dtype() == k_cache.dtype() && q.dtype() == v_cache.dtype(), "q, k, v must have the same data type");
-    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16,
-                "q, k, v only support fp16 or bf16 data type");
+    check_dtype(q, k_cache, v_cache);
     TORCH_CHECK(q.stride(3) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
                 "q, k, v must be contiguous in the last dimension");
-    TORCH_CHECK(q.size(3) % 8 == 0, "hidden dimension must be multiple of 8");
-    TORCH_CHECK(q.size(3) <= 128, "only support hidden dimension <= 128");
-    TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda(), "q, k, v must be on CUDA device");
-    TORCH_CHECK(q.device() == k_cache.device() && q.device() == v_cache.device(),
-                "q, k, v must be on the same CUDA device");
+    check_headdim_device(q, k_cache, v_cache);
     const int64_t bs = q.size(0);
     TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
                     block_table.size(1) > 0,
@@ -597,57 +551,26 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     TORCH_CHECK(block_table.device() == q.device() && cache_seqlens.device() == q.device(),
                 "block_table and cache_seqlens must be on the device of q");
     c10::DeviceGuard device_guard(q.device());
-    TORCH_CHECK(device_is_gfx950(q.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(q.device());
 
     // the pool is read where it is; only a pool whose strides are not 16-byte multiples is copied
-    torch::Tensor qx = aligned16(q) ? q : q.contiguous();
-    torch::Tensor kx = aligned16(k_cache) ? k_cache : k_cache.contiguous();
-    torch::Tensor vx = aligned16(v_cache) ? v_cache : v_cache.contiguous();
+    torch::Tensor qx = aligned_or_contiguous(q);
+    torch::Tensor kx = aligned_or_contiguous(k_cache);
+    torch::Tensor vx = aligned_or_contiguous(v_cache);
     torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
     torch::Tensor sl = cache_seqlens.contiguous();
-
-    int64_t head_q = qx.size(1), seqlen_q = qx.size(2);
-    const int64_t head_kv = kx.size(1), headdim = qx.size(3), g = head_q / head_kv;
-    // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
-    const bool pack = seqlen_q == 1;
-    if (pack) {
-        head_q = head_kv;
-        seqlen_q = g;
+    if (qx.size(2) == 1) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
+        qx = pack_head_q(qx, kx.size(1));
         causal = false;
-        qx = qx.reshape({bs, head_q, seqlen_q, headdim});
-        if (!aligned16(qx)) qx = qx.contiguous();
     }
-    auto o = torch::empty_like(qx);
-    if (!aligned16(o)) o = torch::empty(qx.sizes(), qx.options());
+    auto o = alloc_out_like(qx);
 
     fa_paged_params pp;
     fa_fwd_params &params = pp.base;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = bs;
-    params.num_heads_q = head_q;
-    params.num_heads_kv = head_kv;
-    params.seqlen_q = seqlen_q;
+    fill_params(params, qx, kx, vx, o, softmax_scale);  // (k / v batch stride: the page stride)
     params.seqlen_kv = bt.size(1) * kx.size(2);
-    params.headdim = headdim;
-    params.head_q_per_group = pack ? 1 : g;
-    params.q_batch_stride = stride_or_zero(qx, 0);
-    params.k_batch_stride = stride_or_zero(kx, 0);  // the page stride
-    params.v_batch_stride = stride_or_zero(vx, 0);
-    params.o_batch_stride = stride_or_zero(o, 0);
-    params.q_head_stride = stride_or_zero(qx, 1);
-    params.k_head_stride = stride_or_zero(kx, 1);
-    params.v_head_stride = stride_or_zero(vx, 1);
-    params.o_head_stride = stride_or_zero(o, 1);
-    params.q_seqlen_stride = stride_or_zero(qx, 2);
     params.k_seqlen_stride = kx.stride(2);
     params.v_seqlen_stride = vx.stride(2);
-    params.o_seqlen_stride = stride_or_zero(o, 2);
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
     pp.block_table = bt.data_ptr<int32_t>();
     pp.block_table_stride = bt.stride(0);
     pp.max_pages = bt.size(1);
@@ -655,17 +578,13 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     pp.page_size = kx.size(2);
     pp.seqlens_k = sl.data_ptr<int32_t>();
 
-    const int dtype = qx.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    void *stream = c10::hip::getCurrentHIPStream(qx.device().index()).stream();
+    const int dtype = fa_dtype(qx);
     const int64_t ws_bytes = fa_fwd_gfx950_paged_workspace_size(&pp, dtype, causal ? 1 : 0);
     TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws;
-    if (ws_bytes > 0) ws = torch::empty({ws_bytes}, qx.options().dtype(torch::kUInt8));
-    const int rc = fa_fwd_gfx950_paged(&pp, dtype, causal ? 1 : 0, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
-                                       stream);
-    TORCH_CHECK(rc == FA_OK, "fa_fwd_gfx950_paged failed (code ", rc, "): ", fa_last_error());
-    if (o.sizes() != q.sizes()) o = o.reshape(q.sizes());
-    return o;
+    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+    check_rc(fa_fwd_gfx950_paged(&pp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
+             "fa_fwd_gfx950_paged");
+    return shaped_like(o, q);
 }
 
 // In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
@@ -746,8 +665,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
         }
     }
     c10::DeviceGuard device_guard(k_cache.device());
-    TORCH_CHECK(device_is_gfx950(k_cache.device().index()),
-                "flash attention (gfx950 build) is only supported on MI355X / gfx950 devices");
+    require_gfx950(k_cache.device());
 
     const int64_t page_size = k_cache.size(2), max_pages = paged ? block_table->size(1) : 1;
     torch::Tensor q_rot = q.has_value() ? torch::empty(q->sizes(), q->options()) : torch::empty({0}, k_cache.options());
@@ -807,10 +725,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
     p.seqlen_new = sn;
     p.seqlen_q = sq;
     p.headdim = d;
-    const int dtype = k_cache.scalar_type() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
-    void *stream = c10::hip::getCurrentHIPStream(k_cache.device().index()).stream();
-    const int rc = fa_kvcache_append_gfx950(&p, dtype, stream);
-    TORCH_CHECK(rc == FA_OK, "fa_kvcache_append_gfx950 failed (code ", rc, "): ", fa_last_error());
+    check_rc(fa_kvcache_append_gfx950(&p, fa_dtype(k_cache), current_stream(k_cache)), "fa_kvcache_append_gfx950");
     return {new_seqlens, q_rot};
 }
 

@@ -38,6 +38,39 @@ except Exception as e:  # noqa: BLE001 -- surfaced when a GPU tensor reaches the
     _load_error = e
 
 
+def _require_ext() -> None:
+    """A GPU tensor reached an op but the extension did not load: an error, never another implementation."""
+    if flash_attention_cuda is None:
+        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+
+
+def _default_scale(q: torch.Tensor, softmax_scale):
+    """``D ** -0.5`` on the UNPADDED head dim unless the caller gave a scale (reference :49-50)."""
+    return (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+
+
+def _padded_call(fn, tensors, *args):
+    """``fn(*tensors, *args)`` as every "cuda" kernel calls the extension (reference :19-38): the tensors'
+    head dim (their last) zero-padded to a multiple of 8 and made contiguous, the padding sliced off the
+    result again."""
+    head_dim = tensors[0].size(-1)
+    pad = -head_dim % 8
+    if pad:
+        tensors = [torch.nn.functional.pad(t, [0, pad]) for t in tensors]
+    attn = fn(*[t if t.stride(-1) == 1 else t.contiguous() for t in tensors], *args)
+    return attn[..., :head_dim] if pad else attn
+
+
+def _masked_sdpa(q, k, v, mask, softmax_scale):
+    """torch SDPA with the kernel's semantics, for the CPU defaults: GQA, ``mask`` [Sq, Sk] bool (True =
+    visible, or None), rows that see no key 0 as on the GPU."""
+    o = torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=softmax_scale,
+                                                         enable_gqa=True)
+    if mask is not None:
+        o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
+    return o
+
+
 @torch.library.custom_op("flash_attention::forward", mutates_args=())
 def flash_attention_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_scale: float = None,
                             causal: bool = False) -> torch.Tensor:
@@ -51,22 +84,8 @@ def flash_attention_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, s
 @torch.library.register_kernel("flash_attention::forward", "cuda")
 def flash_attention_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_scale: float = None,
                                  causal: bool = False) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
-    head_dim = q.size(3)
-    need_padding = head_dim % 8 != 0
-    if need_padding:
-        pad = [0, 8 - head_dim % 8]
-        q = torch.nn.functional.pad(q, pad)
-        k = torch.nn.functional.pad(k, pad)
-        v = torch.nn.functional.pad(v, pad)
-    q = q.contiguous() if q.stride(3) != 1 else q
-    k = k.contiguous() if k.stride(3) != 1 else k
-    v = v.contiguous() if v.stride(3) != 1 else v
-    attn = flash_attention_cuda.flash_attention_fwd(q, k, v, softmax_scale, causal)
-    if need_padding:
-        attn = attn[:, :, :, :head_dim]
-    return attn
+    _require_ext()
+    return _padded_call(flash_attention_cuda.flash_attention_fwd, (q, k, v), softmax_scale, causal)
 
 
 @torch.library.register_fake("flash_attention::forward")
@@ -77,7 +96,7 @@ def flash_attention_forward_fake(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
 
 def flash_attn_func(q, k, v, softmax_scale=None, causal=False):
     # q: [batch_size, n_heads, q_seq_len, d]; k, v: [batch_size, n_heads_kv, kv_seq_len, d]
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     return torch.ops.flash_attention.forward(q, k, v, softmax_scale, causal)
 
 
@@ -122,11 +141,7 @@ def flash_attention_varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Te
             mask = _window_mask(q1 - q0, k1 - k0, window_left, causal, q.device)
         else:
             mask = _bottom_right_causal(q1 - q0, k1 - k0, q.device) if causal else None
-        o = torch.nn.functional.scaled_dot_product_attention(qs, ks, vs, attn_mask=mask, scale=softmax_scale,
-                                                             enable_gqa=True)
-        if mask is not None:  # rows with no visible key (Sq_b > Sk_b) are 0, as on the GPU
-            o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
-        out[q0:q1] = o[0].transpose(0, 1)
+        out[q0:q1] = _masked_sdpa(qs, ks, vs, mask, softmax_scale)[0].transpose(0, 1)
     return out
 
 
@@ -135,23 +150,9 @@ def flash_attention_varlen_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: tor
                                         cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
                                         max_seqlen_k: int, softmax_scale: float = None,
                                         causal: bool = False, window_left: int = -1) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
-    head_dim = q.size(2)
-    need_padding = head_dim % 8 != 0
-    if need_padding:
-        pad = [0, 8 - head_dim % 8]
-        q = torch.nn.functional.pad(q, pad)
-        k = torch.nn.functional.pad(k, pad)
-        v = torch.nn.functional.pad(v, pad)
-    q = q.contiguous() if q.stride(2) != 1 else q
-    k = k.contiguous() if k.stride(2) != 1 else k
-    v = v.contiguous() if v.stride(2) != 1 else v
-    attn = flash_attention_cuda.flash_attention_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                                                           max_seqlen_k, softmax_scale, causal, int(window_left))
-    if need_padding:
-        attn = attn[:, :, :head_dim]
-    return attn
+    _require_ext()
+    return _padded_call(flash_attention_cuda.flash_attention_varlen_fwd, (q, k, v), cu_seqlens_q, cu_seqlens_k,
+                        max_seqlen_q, max_seqlen_k, softmax_scale, causal, int(window_left))
 
 
 @torch.library.register_fake("flash_attention::varlen_forward")
@@ -183,7 +184,7 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     With ``FA_CHECK_VARLEN=1`` in the environment (read at every call) both are verified against
     ``cu_seqlens_*`` (one host sync per call; off by default, as in the reference's varlen API).
     ``window_left >= 0``: the local window of ``flash_attn_window_func`` within each sequence."""
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     if _check_varlen_enabled():
         _check_varlen_maxima(cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
     return torch.ops.flash_attention.varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
@@ -219,12 +220,8 @@ def flash_attention_padded_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Te
         else:
             # bottom-right per sequence (one query row sees every key, as the Sq == 1 pack's non-causal)
             mask = _bottom_right_causal(q1 - q0, k1 - k0, q.device) if causal else None
-        o = torch.nn.functional.scaled_dot_product_attention(q[b:b + 1, :, q0:q1], k[b:b + 1, :, k0:k1],
-                                                             v[b:b + 1, :, k0:k1], attn_mask=mask,
-                                                             scale=softmax_scale, enable_gqa=True)
-        if mask is not None:
-            o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
-        out[b:b + 1, :, q0:q1] = o
+        out[b:b + 1, :, q0:q1] = _masked_sdpa(q[b:b + 1, :, q0:q1], k[b:b + 1, :, k0:k1], v[b:b + 1, :, k0:k1], mask,
+                                              softmax_scale)
     return out
 
 
@@ -233,23 +230,9 @@ def flash_attention_padded_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: tor
                                         k_end: torch.Tensor, q_start: Optional[torch.Tensor] = None,
                                         q_end: Optional[torch.Tensor] = None, softmax_scale: float = None,
                                         causal: bool = False, window_left: int = -1) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
-    head_dim = q.size(3)
-    need_padding = head_dim % 8 != 0
-    if need_padding:
-        pad = [0, 8 - head_dim % 8]
-        q = torch.nn.functional.pad(q, pad)
-        k = torch.nn.functional.pad(k, pad)
-        v = torch.nn.functional.pad(v, pad)
-    q = q.contiguous() if q.stride(3) != 1 else q
-    k = k.contiguous() if k.stride(3) != 1 else k
-    v = v.contiguous() if v.stride(3) != 1 else v
-    attn = flash_attention_cuda.flash_attention_padded_fwd(q, k, v, q_start, q_end, k_start, k_end, softmax_scale,
-                                                           causal, int(window_left))
-    if need_padding:
-        attn = attn[:, :, :, :head_dim]
-    return attn
+    _require_ext()
+    return _padded_call(flash_attention_cuda.flash_attention_padded_fwd, (q, k, v), q_start, q_end, k_start, k_end,
+                        softmax_scale, causal, int(window_left))
 
 
 @torch.library.register_fake("flash_attention::padded_forward")
@@ -266,7 +249,7 @@ def flash_attn_padded_func(q, k, v, k_start, k_end, q_start=None, q_end=None, so
     on q's device; default: every query row). Causal / window masks are bottom-right aligned per
     sequence; output rows outside the query ranges are 0. No host synchronisation (graph-capturable);
     Sq == 1 takes the q-head pack and the split-KV decode kernel."""
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     return torch.ops.flash_attention.padded_forward(q, k, v, k_start, k_end, q_start, q_end, softmax_scale, causal,
                                                     int(window_left))
 
@@ -295,8 +278,7 @@ def flash_attention_rope_apply(x: torch.Tensor, cos: torch.Tensor, sin: torch.Te
 
 @torch.library.register_kernel("flash_attention::rope_apply", "cuda")
 def flash_attention_rope_apply_cuda(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    _require_ext()
     x = x.contiguous() if x.stride(3) != 1 else x
     return flash_attention_cuda.rope_apply(x, cos.to(x.dtype), sin.to(x.dtype))
 
@@ -319,15 +301,11 @@ def flash_attention_rope_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
 def flash_attention_rope_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor,
                                       sin: torch.Tensor, softmax_scale: float = None,
                                       causal: bool = False) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    _require_ext()
     cos, sin = cos.to(q.dtype), sin.to(q.dtype)
     if q.size(3) % 8 != 0:  # padded head dims: rotate first (the halves are those of the real D)
         return flash_attention_forward_cuda(flash_attention_rope_apply_cuda(q, cos, sin), k, v, softmax_scale, causal)
-    q = q.contiguous() if q.stride(3) != 1 else q
-    k = k.contiguous() if k.stride(3) != 1 else k
-    v = v.contiguous() if v.stride(3) != 1 else v
-    return flash_attention_cuda.flash_attention_rope_fwd(q, k, v, cos, sin, softmax_scale, causal)
+    return _padded_call(flash_attention_cuda.flash_attention_rope_fwd, (q, k, v), cos, sin, softmax_scale, causal)
 
 
 @torch.library.register_fake("flash_attention::rope_forward")
@@ -343,7 +321,7 @@ def apply_rope(x, cos, sin):
 def flash_attn_rope_func(q, k, v, cos, sin, softmax_scale=None, causal=False):
     """``flash_attn_func(apply_rope(q, cos, sin), k, v, ...)`` with the rotation of q fused into the
     attention kernel's Q load; k must already be rotated (``apply_rope``)."""
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     return torch.ops.flash_attention.rope_forward(q, k, v, cos, sin, softmax_scale, causal)
 
 
@@ -369,33 +347,17 @@ def flash_attention_window_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     # q: [B, Hq, Sq, D]; k, v: [B, Hkv, Sk, D]. Non-GPU default: torch SDPA under the window mask
     # (GQA expanded; rows that see no key are 0, as on the GPU).
     warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
-    mask = _window_mask(q.size(2), k.size(2), window_left, causal, q.device)
-    o = torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=softmax_scale,
-                                                         enable_gqa=True)
-    return o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
+    return _masked_sdpa(q, k, v, _window_mask(q.size(2), k.size(2), window_left, causal, q.device), softmax_scale)
 
 
 @torch.library.register_kernel("flash_attention::window_forward", "cuda")
 def flash_attention_window_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, window_left: int,
                                         softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    _require_ext()
     if window_left < 0:
         raise ValueError(f"window_left must be >= 0 (got {window_left})")
-    head_dim = q.size(3)
-    need_padding = head_dim % 8 != 0
-    if need_padding:
-        pad = [0, 8 - head_dim % 8]
-        q = torch.nn.functional.pad(q, pad)
-        k = torch.nn.functional.pad(k, pad)
-        v = torch.nn.functional.pad(v, pad)
-    q = q.contiguous() if q.stride(3) != 1 else q
-    k = k.contiguous() if k.stride(3) != 1 else k
-    v = v.contiguous() if v.stride(3) != 1 else v
-    attn = flash_attention_cuda.flash_attention_window_fwd(q, k, v, int(window_left), softmax_scale, causal)
-    if need_padding:
-        attn = attn[:, :, :, :head_dim]
-    return attn
+    return _padded_call(flash_attention_cuda.flash_attention_window_fwd, (q, k, v), int(window_left), softmax_scale,
+                        causal)
 
 
 @torch.library.register_fake("flash_attention::window_forward")
@@ -408,7 +370,7 @@ def flash_attn_window_func(q, k, v, window_left, softmax_scale=None, causal=Fals
     window of ``window_left + 1`` keys ending at the (bottom-right) diagonal with ``causal``.
     transformers' ``sliding_window`` W is ``window_left = W - 1`` (flash-attn ``window_size=(W - 1,
     -1)``)."""
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     return torch.ops.flash_attention.window_forward(q, k, v, int(window_left), softmax_scale, causal)
 
 
@@ -453,11 +415,7 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
         kb = k_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
         vb = v_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
         mask = _bottom_right_causal(sq, n, q.device) if causal else None
-        o = torch.nn.functional.scaled_dot_product_attention(q[b:b + 1], kb, vb, attn_mask=mask, scale=softmax_scale,
-                                                             enable_gqa=True)
-        if mask is not None:
-            o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
-        out[b:b + 1] = o
+        out[b:b + 1] = _masked_sdpa(q[b:b + 1], kb, vb, mask, softmax_scale)
     return out
 
 
@@ -465,8 +423,7 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
 def flash_attention_paged_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                                        block_table: torch.Tensor, cache_seqlens: torch.Tensor,
                                        softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    _require_ext()
     g, sq = q.size(1) // k_cache.size(1), q.size(2)
     if g * sq > _PAGED_DECODE_MAX_ROWS:
         # the copying path: the kernel serves decode shapes only, larger query blocks (a chunked prefill
@@ -476,21 +433,9 @@ def flash_attention_paged_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v
         v = _gather_pages(v_cache, block_table)
         return flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None,
                                                    None, softmax_scale, causal, -1)
-    head_dim = q.size(3)
-    need_padding = head_dim % 8 != 0
-    if need_padding:  # (pads the pool: a copy of it)
-        pad = [0, 8 - head_dim % 8]
-        q = torch.nn.functional.pad(q, pad)
-        k_cache = torch.nn.functional.pad(k_cache, pad)
-        v_cache = torch.nn.functional.pad(v_cache, pad)
-    q = q.contiguous() if q.stride(3) != 1 else q
-    k_cache = k_cache.contiguous() if k_cache.stride(3) != 1 else k_cache
-    v_cache = v_cache.contiguous() if v_cache.stride(3) != 1 else v_cache
-    attn = flash_attention_cuda.flash_attention_paged_fwd(q, k_cache, v_cache, block_table, cache_seqlens,
-                                                          softmax_scale, causal)
-    if need_padding:
-        attn = attn[:, :, :, :head_dim]
-    return attn
+    # (a head dim that is no multiple of 8 pads the pool: a copy of it)
+    return _padded_call(flash_attention_cuda.flash_attention_paged_fwd, (q, k_cache, v_cache), block_table,
+                        cache_seqlens, softmax_scale, causal)
 
 
 @torch.library.register_fake("flash_attention::paged_forward")
@@ -513,7 +458,7 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     query blocks take the COPYING path: the table's pages are gathered into a dense cache
     (``index_select``) for ``flash_attn_padded_func``. Neither path synchronises with the host, so both
     can be captured in a graph."""
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     return torch.ops.flash_attention.paged_forward(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale,
                                                    causal)
 
@@ -577,8 +522,7 @@ def flash_attention_kvcache_append_cuda(k_cache: torch.Tensor, v_cache: torch.Te
                                         block_table: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
                                         rotary_cos: Optional[torch.Tensor] = None,
                                         rotary_sin: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
-    if flash_attention_cuda is None:
-        raise RuntimeError(f"gfx950 flash attention extension is not available: {_load_error!r}")
+    _require_ext()
     # the inputs may be copied to make their last dimension contiguous; the caches never are (a copy would
     # swallow the write): the binding rejects a cache whose last dimension is not contiguous
     k, v, q = (t.contiguous() if t is not None and t.stride(3) != 1 else t for t in (k, v, q))
@@ -636,7 +580,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         raise ValueError("k and v must be given together")
     if (rotary_cos is None) != (rotary_sin is None):
         raise ValueError("rotary_cos and rotary_sin must be given together")
-    softmax_scale = (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    softmax_scale = _default_scale(q, softmax_scale)
     new_seqlens, q_rot = cache_seqlens, q
     if rotary_cos is not None:  # (cast as apply_rope casts its tables)
         new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append(

@@ -132,6 +132,10 @@ def test_paged_serves_decode_shapes_only(lib):
     rc, err = check(lib, p, causal=1)
     assert rc == FA_ERR_UNSUPPORTED and "decode rule" in err and "head_q_per_group * seqlen_q" in err
     assert lib.fa_fwd_gfx950_paged(ctypes.byref(p), 1, 1, None, 0, None) == FA_ERR_UNSUPPORTED
+    # one row past the rule (fa_launch.h decode_rule, shared with the dense dispatcher): 5 heads x 13 = 65
+    rc, err = check(lib, paged_params(hq=40, sq=13, pack=False))
+    assert rc == FA_ERR_UNSUPPORTED and "decode shapes only" in err and "got 65" in err
+    assert check(lib, paged_params(hq=32, sq=16, pack=False))[0] == FA_OK  # 64 rows
     assert lib.fa_fwd_gfx950_paged_check(None, 1, 0) == FA_ERR_INVALID_ARGUMENT
     from flash_attention_cute_amd import _debug
 
