@@ -9,3 +9,4 @@ from .flash_attention import flash_attn_varlen_func  # noqa: F401  (beyond the r
 from .flash_attention import flash_attn_paged_func  # noqa: F401  (beyond the reference: paged KV cache)
 from .flash_attention import flash_attn_kvcache_append, flash_attn_with_kvcache  # noqa: F401  (beyond the reference)
 from .flash_attention import flash_attention_kvcache_append  # noqa: F401  (the custom op's function)
+from .flash_attention import flash_attention_kvcache_append_fp8, flash_attention_paged_forward_fp8  # noqa: F401  (FP8 cache)

@@ -28,6 +28,10 @@ from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond th
     flash_attn_kvcache_append,
     flash_attn_with_kvcache,
 )
+from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond the reference: FP8 KV cache)
+    flash_attention_kvcache_append_fp8,
+    flash_attention_paged_forward_fp8,
+)
 
 from .load_cpp_extention import load_extension  # noqa: F401  (the reference module imports it, :2)
 

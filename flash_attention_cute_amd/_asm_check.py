@@ -393,6 +393,10 @@ def check_file(path) -> list[str]:
         if "fa_decode_paged" not in text:
             return [f"{path}: no fa_decode_paged kernel in the assembly (stale or wrong file)"]
         return spills(text)
+    if "fa_paged_fp8_inst" in str(path):  # the FP8 paged decode kernels (csrc/fa_paged_fp8_inst.hip)
+        if "fa_decode_fp8kv" not in text:
+            return [f"{path}: no fa_decode_fp8kv kernel in the assembly (stale or wrong file)"]
+        return spills(text)
     if "fa_fwd_w4" not in text:
         return [f"{path}: no fa_fwd_w4 kernel in the assembly (stale or wrong file)"]
     return agpr_violations(text) + spills(text) + hazards(text)

@@ -7,10 +7,12 @@ into the package directory so the artefacts travel with the repository snapshot.
 
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
      head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_paged_inst.hip x 16 (the
-     paged decode kernels, the same combinations) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip
-     (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip (stand-alone kernels with their entries)
-     ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h and
-     include/fa_gfx950_kvcache.h; no torch symbols)
+     paged decode kernels, the same combinations) + csrc/fa_paged_fp8_inst.hip x 16 (the FP8 paged decode
+     kernels) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip, csrc/fa_paged_fp8_gfx950.hip (C-ABI
+     dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip (stand-alone kernels with
+     their entries)
+     ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
+     include/fa_gfx950_kvcache.h and include/fa_gfx950_fp8.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -159,8 +161,23 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
                       f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
                       "-Wno-inline-asm", "-c", CSRC / "fa_paged_inst.hip", "-o", obj], obj, paged_deps + tooling))
-    # C-ABI dispatchers (dense, paged), standalone RoPE kernel, KV-cache append kernel
-    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip"):
+    # the FP8 paged decode kernels (csrc/fa_paged_fp8_inst.hip), the same combinations again, in directories
+    # whose names match neither pattern above; their objects also depend on the public headers
+    fp8_deps = inst_deps + [CSRC / "fa_paged_fp8_inst.hip", *sorted(INCLUDE.glob("*.h"))]
+    for dt, c, d, e in INSTANCES:
+        idir = objdir / f"fp8_{dt.lower()}_c{c}_d{d}_x{e}"
+        idir.mkdir(parents=True, exist_ok=True)
+        obj = idir / "fa_paged_fp8_inst.o"
+        objs.append(obj)
+        stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
+        if not stub:
+            asm_files.append(idir / f"fa_paged_fp8_inst-hip-amdgcn-amd-amdhsa-{ARCH}.s")
+        cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
+                      f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
+                      "-Wno-inline-asm", "-c", CSRC / "fa_paged_fp8_inst.hip", "-o", obj], obj, fp8_deps + tooling))
+    # C-ABI dispatchers (dense, paged, FP8 paged), standalone RoPE kernel, KV-cache append kernels
+    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_fp8_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip",
+                "fa_kvcache_fp8.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src, "-o", obj], obj,
@@ -170,7 +187,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         stamp = obj.with_suffix(".cmd")
         line = " ".join(map(str, cmd))
         if (not force and not _stale(obj, deps) and stamp.exists() and stamp.read_text() == line
-                and (obj.name not in ("fa_inst.o", "fa_paged_inst.o") or next(obj.parent.glob("*.s"), None) is not None)):
+                and (obj.name not in ("fa_inst.o", "fa_paged_inst.o", "fa_paged_fp8_inst.o") or next(obj.parent.glob("*.s"), None) is not None)):
             return
         _run(cmd, verbose)
         stamp.write_text(line)
@@ -206,8 +223,7 @@ def build_ext(force: bool = False, verbose: bool = False) -> Path:
     lib = build_abi(force=force, verbose=verbose)
     out = ext_path()
     src = CSRC / "flash_attention_api.cpp"
-    if not force and not _stale(out, [src, INCLUDE / "fa_gfx950.h", INCLUDE / "fa_gfx950_paged.h",
-                                      INCLUDE / "fa_gfx950_kvcache.h", lib]):
+    if not force and not _stale(out, [src, *sorted(INCLUDE.glob("*.h")), lib]):
         return out
     incs = cpp_extension.include_paths(device_type="cuda")
     libdirs = cpp_extension.library_paths(device_type="cuda")

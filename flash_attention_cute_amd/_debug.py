@@ -20,7 +20,7 @@ import ctypes
 from . import _build
 
 PATHS = {0: "none", 1: "w4", 2: "w8", 3: "w4slow", 4: "decode", 5: "decode_split", 6: "p8", 7: "m32", 8: "m16",
-         9: "decode_paged", 10: "decode_paged_split"}
+         9: "decode_paged", 10: "decode_paged_split", 11: "decode_paged_fp8", 12: "decode_paged_fp8_split"}
 VARIANTS = {"w4": 0, "w8": 1, "w4slow": 2, "p8": 3, "m32": 4, "m16": 5}
 LOG2E = 1.4426950408889634
 

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "fa_gfx950.h"
+#include "fa_gfx950_fp8.h"
 #include "fa_gfx950_kvcache.h"
 #include "fa_gfx950_paged.h"
 
@@ -526,9 +527,44 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // pool is read in place: no gather, no host synchronisation (graph-capturable). Decode shapes only
 // (g * Sq <= 64; the Python op gathers larger query blocks); Sq == 1 takes the q-head pack of
 // flash_attention_fwd. No reference counterpart.
-torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
-                                        torch::Tensor &block_table, torch::Tensor &cache_seqlens,
-                                        float softmax_scale, bool causal) {
+//
+// fp8 (flash_attention_paged_fp8_fwd, include/fa_gfx950_fp8.h fa_fwd_gfx950_paged_fp8): the caches are
+// torch.float8_e4m3fn pools read in place (never copied: 16-byte aligned, strides multiples of 16), q / o
+// stay fp16 / bf16, k_descale / v_descale are fp32 [B, Hkv] device tensors of any strides (undefined: 1.0).
+struct Fp8Descales {
+    const torch::Tensor *k, *v;  // nullptr / undefined tensor: 1.0
+};
+
+// the [B, Hkv] fp32 descales of an fp8 entry: pointers and the strides both share
+void fill_descales(const Fp8Descales &ds, const torch::Tensor &like, int64_t bs, int64_t hkv, const float *&kd,
+                   const float *&vd, int64_t &batch_stride, int64_t &head_stride, torch::Tensor &keep_k,
+                   torch::Tensor &keep_v) {
+    auto prep = [&](const torch::Tensor *t, const char *name) {
+        if (!t || !t->defined()) return torch::Tensor();
+        TORCH_CHECK(t->dtype() == torch::kFloat32 && t->dim() == 2 && t->size(0) == bs && t->size(1) == hkv, name,
+                    " must be fp32 [batch, kv heads]");
+        TORCH_CHECK(t->device() == like.device(), name, " must be on the device of q / the caches");
+        return *t;
+    };
+    keep_k = prep(ds.k, "k_descale");
+    keep_v = prep(ds.v, "v_descale");
+    // one stride pair serves both arrays: a tensor laid out differently from the other is made contiguous
+    if (keep_k.defined() && keep_v.defined() &&
+        (stride_or_zero(keep_k, 0) != stride_or_zero(keep_v, 0) || stride_or_zero(keep_k, 1) != stride_or_zero(keep_v, 1) ||
+         keep_k.stride(0) < 0 || keep_k.stride(1) < 0)) {
+        keep_k = keep_k.contiguous();
+        keep_v = keep_v.contiguous();
+    }
+    const torch::Tensor &any = keep_k.defined() ? keep_k : keep_v;
+    kd = keep_k.defined() ? keep_k.data_ptr<float>() : nullptr;
+    vd = keep_v.defined() ? keep_v.data_ptr<float>() : nullptr;
+    batch_stride = any.defined() ? stride_or_zero(any, 0) : 0;
+    head_stride = any.defined() ? stride_or_zero(any, 1) : 0;
+}
+
+torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                             torch::Tensor &block_table, torch::Tensor &cache_seqlens, float softmax_scale,
+                             bool causal, const Fp8Descales *fp8) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
                 "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
     TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
@@ -538,7 +574,13 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
                 "number of heads in q must be multiple of number of heads in k and v");
     TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
-    check_dtype(q, k_cache, v_cache);
+    if (fp8) {
+        TORCH_CHECK(k_cache.dtype() == at::kFloat8_e4m3fn && v_cache.dtype() == at::kFloat8_e4m3fn,
+                    "the fp8 caches must be torch.float8_e4m3fn");
+        check_dtype(q, q, q);
+    } else {
+        check_dtype(q, k_cache, v_cache);
+    }
     TORCH_CHECK(q.stride(3) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
                 "q, k, v must be contiguous in the last dimension");
     check_headdim_device(q, k_cache, v_cache);
@@ -553,10 +595,11 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     c10::DeviceGuard device_guard(q.device());
     require_gfx950(q.device());
 
-    // the pool is read where it is; only a pool whose strides are not 16-byte multiples is copied
+    // the pool is read where it is; only a 16-bit pool whose strides are not 16-byte multiples is copied
+    // (an fp8 pool never: the library rejects one that is not 16-byte aligned)
     torch::Tensor qx = aligned_or_contiguous(q);
-    torch::Tensor kx = aligned_or_contiguous(k_cache);
-    torch::Tensor vx = aligned_or_contiguous(v_cache);
+    torch::Tensor kx = fp8 ? k_cache : aligned_or_contiguous(k_cache);
+    torch::Tensor vx = fp8 ? v_cache : aligned_or_contiguous(v_cache);
     torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
     torch::Tensor sl = cache_seqlens.contiguous();
     if (qx.size(2) == 1) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
@@ -565,7 +608,9 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     }
     auto o = alloc_out_like(qx);
 
-    fa_paged_params pp;
+    fa_paged_fp8_params fp;
+    memset(&fp, 0, sizeof(fp));
+    fa_paged_params &pp = fp.paged;
     fa_fwd_params &params = pp.base;
     fill_params(params, qx, kx, vx, o, softmax_scale);  // (k / v batch stride: the page stride)
     params.seqlen_kv = bt.size(1) * kx.size(2);
@@ -579,12 +624,37 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
     pp.seqlens_k = sl.data_ptr<int32_t>();
 
     const int dtype = fa_dtype(qx);
+    if (fp8) {
+        torch::Tensor keep_k, keep_v;
+        fill_descales(*fp8, q, bs, kx.size(1), fp.k_descale, fp.v_descale, fp.descale_batch_stride,
+                      fp.descale_head_stride, keep_k, keep_v);
+        const int64_t ws_bytes = fa_fwd_gfx950_paged_fp8_workspace_size(&fp, dtype, causal ? 1 : 0);
+        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_fp8_workspace_size failed: ", fa_last_error());
+        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+        check_rc(fa_fwd_gfx950_paged_fp8(&fp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
+                 "fa_fwd_gfx950_paged_fp8");
+        return shaped_like(o, q);
+    }
     const int64_t ws_bytes = fa_fwd_gfx950_paged_workspace_size(&pp, dtype, causal ? 1 : 0);
     TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_workspace_size failed: ", fa_last_error());
     torch::Tensor ws = workspace_for(ws_bytes, qx.options());
     check_rc(fa_fwd_gfx950_paged(&pp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
              "fa_fwd_gfx950_paged");
     return shaped_like(o, q);
+}
+
+torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                        torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                        float softmax_scale, bool causal) {
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, nullptr);
+}
+
+torch::Tensor flash_attention_paged_fp8_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                            torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                            c10::optional<torch::Tensor> k_descale,
+                                            c10::optional<torch::Tensor> v_descale, float softmax_scale, bool causal) {
+    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds);
 }
 
 // In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
@@ -594,16 +664,29 @@ torch::Tensor flash_attention_paged_fwd(torch::Tensor &q, torch::Tensor &k_cache
 // last Sq positions after the append. Returns (new_seqlens int32 [B], q_rot or an empty tensor). The caches
 // are written where they are -- never copied, whatever their alignment -- in one launch with no host
 // synchronisation (graph-capturable). No reference counterpart.
-std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
+//
+// fp8 (flash_attention_kvcache_append_fp8, include/fa_gfx950_fp8.h fa_kvcache_append_fp8_gfx950): the caches
+// are torch.float8_e4m3fn, k / v / q / the tables fp16 or bf16; k (rotated, rounded to its dtype) and v are
+// quantized with the [B, Hkv] descales on the way in, q_rot stays 16-bit.
+std::tuple<torch::Tensor, torch::Tensor> kvcache_append_impl(
     torch::Tensor &k_cache, torch::Tensor &v_cache, c10::optional<torch::Tensor> k, c10::optional<torch::Tensor> v,
     torch::Tensor &cache_seqlens, c10::optional<torch::Tensor> block_table, c10::optional<torch::Tensor> q,
-    c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin) {
+    c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin, const Fp8Descales *fp8) {
     TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4,
                 "the caches must be 4-D [pages, heads, page_size, dim] or [batch, heads, seqlen, dim]");
     TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
     TORCH_CHECK(k_cache.dtype() == v_cache.dtype(), "k_cache, v_cache must have the same data type");
-    TORCH_CHECK(k_cache.dtype() == torch::kHalf || k_cache.dtype() == torch::kBFloat16,
-                "the caches only support fp16 or bf16 data type");
+    // the 16-bit dtype of k / v / q / the tables: the caches' own, or with an fp8 cache the inputs'
+    auto io_dtype = k_cache.dtype();
+    if (fp8) {
+        TORCH_CHECK(k_cache.dtype() == at::kFloat8_e4m3fn, "the fp8 caches must be torch.float8_e4m3fn");
+        io_dtype = k.has_value() ? k->dtype() : q.has_value() ? q->dtype() : caffe2::TypeMeta::Make<at::Half>();
+        TORCH_CHECK(io_dtype == torch::kHalf || io_dtype == torch::kBFloat16,
+                    "k, v and q only support fp16 or bf16 data type");
+    } else {
+        TORCH_CHECK(k_cache.dtype() == torch::kHalf || k_cache.dtype() == torch::kBFloat16,
+                    "the caches only support fp16 or bf16 data type");
+    }
     TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.device() == v_cache.device(),
                 "the caches must be on the same CUDA device");
     TORCH_CHECK(k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
@@ -631,7 +714,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
         TORCH_CHECK(t.dim() == 4 && t.size(0) == bs && t.size(3) == d, name, " must be [batch, heads, seqlen, dim] "
                     "with the batch of cache_seqlens and the caches' hidden dimension");
         TORCH_CHECK(t.size(1) > 0 && t.size(1) % heads_multiple_of == 0, name, ": wrong number of heads");
-        TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+        TORCH_CHECK(t.dtype() == io_dtype, name, fp8 ? " must have the data type of k" : " must have the caches' data type");
         TORCH_CHECK(t.device() == k_cache.device(), name, " must be on the device of the caches");
         TORCH_CHECK(t.stride(3) == 1, name, " must be contiguous in the last dimension");
     };
@@ -652,7 +735,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
         TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
         auto table = [&](const torch::Tensor &t, const char *name) {
             TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
-            TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+            TORCH_CHECK(t.dtype() == io_dtype, name, fp8 ? " must have the data type of k" : " must have the caches' data type");
             TORCH_CHECK(t.device() == k_cache.device(), name, " must be on the device of the caches");
             return t.stride(1) == 1 ? t : t.contiguous();
         };
@@ -668,7 +751,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
     require_gfx950(k_cache.device());
 
     const int64_t page_size = k_cache.size(2), max_pages = paged ? block_table->size(1) : 1;
-    torch::Tensor q_rot = q.has_value() ? torch::empty(q->sizes(), q->options()) : torch::empty({0}, k_cache.options());
+    torch::Tensor q_rot = q.has_value() ? torch::empty(q->sizes(), q->options())
+                                        : torch::empty({0}, k_cache.options().dtype(io_dtype));
     if (bs == 0 || (sn == 0 && sq == 0))  // nothing to launch: the lengths, clamped as the kernel clamps them
         return {cache_seqlens.clamp(0, max_pages * page_size), q_rot};
     torch::Tensor sl = cache_seqlens.contiguous();
@@ -676,8 +760,21 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
     torch::Tensor bt;
     if (paged) bt = block_table->stride(1) == 1 ? *block_table : block_table->contiguous();
 
-    fa_kvcache_params p;
-    memset(&p, 0, sizeof(p));
+    if (fp8) {  // the quantizing kernel moves 16 bytes per load: inputs that are not so aligned are copied
+        if (k.has_value()) {
+            k = aligned_or_contiguous(*k);
+            v = aligned_or_contiguous(*v);
+        }
+        if (q.has_value()) q = aligned_or_contiguous(*q);
+        if (cs.defined() && (cs.stride(0) % 8 != 0 || reinterpret_cast<uintptr_t>(cs.data_ptr()) % 16 != 0 ||
+                             reinterpret_cast<uintptr_t>(sn_t.data_ptr()) % 16 != 0)) {
+            cs = cs.clone(at::MemoryFormat::Contiguous);
+            sn_t = sn_t.clone(at::MemoryFormat::Contiguous);
+        }
+    }
+    fa_kvcache_fp8_params fp;
+    memset(&fp, 0, sizeof(fp));
+    fa_kvcache_params &p = fp.base;
     if (sn > 0) {
         p.k_new = k->data_ptr();
         p.v_new = v->data_ptr();
@@ -725,8 +822,32 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
     p.seqlen_new = sn;
     p.seqlen_q = sq;
     p.headdim = d;
+    if (fp8) {
+        torch::Tensor keep_k, keep_v;
+        fill_descales(*fp8, k_cache, bs, hkv, fp.k_descale, fp.v_descale, fp.descale_batch_stride,
+                      fp.descale_head_stride, keep_k, keep_v);
+        const int dtype = io_dtype == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
+        check_rc(fa_kvcache_append_fp8_gfx950(&fp, dtype, current_stream(k_cache)), "fa_kvcache_append_fp8_gfx950");
+        return {new_seqlens, q_rot};
+    }
     check_rc(fa_kvcache_append_gfx950(&p, fa_dtype(k_cache), current_stream(k_cache)), "fa_kvcache_append_gfx950");
     return {new_seqlens, q_rot};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append(
+    torch::Tensor &k_cache, torch::Tensor &v_cache, c10::optional<torch::Tensor> k, c10::optional<torch::Tensor> v,
+    torch::Tensor &cache_seqlens, c10::optional<torch::Tensor> block_table, c10::optional<torch::Tensor> q,
+    c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin) {
+    return kvcache_append_impl(k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin, nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_fp8(
+    torch::Tensor &k_cache, torch::Tensor &v_cache, c10::optional<torch::Tensor> k, c10::optional<torch::Tensor> v,
+    torch::Tensor &cache_seqlens, c10::optional<torch::Tensor> block_table, c10::optional<torch::Tensor> q,
+    c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin,
+    c10::optional<torch::Tensor> k_descale, c10::optional<torch::Tensor> v_descale) {
+    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    return kvcache_append_impl(k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin, &ds);
 }
 
 }  // namespace flash_attention
@@ -750,4 +871,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_kvcache_append", &flash_attention::flash_attention_kvcache_append,
           "In-place KV-cache append (paged or dense) with fused rotate-half RoPE of k and q, one HIP launch (gfx950)");
     m.def("kvcache_version", []() { return fa_kvcache_version(); });
+    m.def("flash_attention_paged_fp8_fwd", &flash_attention::flash_attention_paged_fp8_fwd,
+          "FlashAttention-2 decode over a paged FP8 (e4m3) KV cache read in place, fp16 / bf16 q and o, gfx950");
+    m.def("flash_attention_kvcache_append_fp8", &flash_attention::flash_attention_kvcache_append_fp8,
+          "Quantizing in-place append to an FP8 (e4m3) KV cache with fused rotate-half RoPE, one HIP launch (gfx950)");
+    m.def("fp8_version", []() { return fa_fp8_version(); });
 }

@@ -444,7 +444,8 @@ def flash_attention_paged_forward_fake(q, k_cache, v_cache, block_table, cache_s
     return torch.empty_like(q)
 
 
-def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False):
+def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False,
+                          k_descale=None, v_descale=None):
     """Attention of q [B, Hq, Sq, D] -- each sequence's LAST Sq positions -- over a paged KV cache:
     ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] with any strides (flash-attn's
     [num_pages, page_size, Hkv, D] is ``cache.transpose(1, 2)``), ``page_size`` a multiple of 32;
@@ -457,8 +458,19 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     Decode shapes (``Hq / Hkv * Sq <= 64``) read the pool in place with the paged split-KV kernel. Larger
     query blocks take the COPYING path: the table's pages are gathered into a dense cache
     (``index_select``) for ``flash_attn_padded_func``. Neither path synchronises with the host, so both
-    can be captured in a graph."""
+    can be captured in a graph.
+
+    An FP8 cache (``torch.float8_e4m3fn`` pools, 16-byte aligned, D a multiple of 16; q and the output stay
+    fp16 / bf16) is read in place by the FP8 paged kernel with the descales ``k_descale`` / ``v_descale``
+    (fp32 [B, Hkv] on q's device, any strides; a Python float is expanded; None is 1.0): ``out = v_descale *
+    softmax(softmax_scale * k_descale * q . K8^T) . V8`` with the bytes widened exactly. Its copying path
+    multiplies the widened K by ``k_descale`` in q's dtype, which rounds K once more."""
     softmax_scale = _default_scale(q, softmax_scale)
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        b, hkv = q.size(0), k_cache.size(1)
+        return torch.ops.flash_attention.paged_forward_fp8(
+            q, k_cache, v_cache, block_table, cache_seqlens, _descale_arg(k_descale, "k_descale", b, hkv, q.device),
+            _descale_arg(v_descale, "v_descale", b, hkv, q.device), softmax_scale, causal)
     return torch.ops.flash_attention.paged_forward(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale,
                                                    causal)
 
@@ -541,7 +553,7 @@ def flash_attention_kvcache_append_fake(k_cache, v_cache, k, v, cache_seqlens, b
 
 
 def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rotary_cos=None,
-                              rotary_sin=None):
+                              rotary_sin=None, k_descale=None, v_descale=None):
     """Append the new keys / values ``k`` / ``v`` [B, Hkv, Sn, D] to a KV cache IN PLACE, one HIP launch:
     token i of sequence b is written at position ``n = cache_seqlens[b] + i`` -- row ``n % page_size`` of
     page ``block_table[b, n // page_size]`` of the pools ``k_cache`` / ``v_cache`` [num_pages, Hkv,
@@ -556,14 +568,25 @@ def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table
     which clamps ids, because a clamped write would corrupt another sequence's page. Negative lengths
     count as 0; positions past the tables use their last row. Two sequences that write the same physical
     row are the caller's error. The caches are never copied (any strides with a contiguous last dimension,
-    any alignment); no host synchronisation, so the call can be captured in a graph."""
+    any alignment); no host synchronisation, so the call can be captured in a graph.
+
+    An FP8 cache (``torch.float8_e4m3fn``; k / v fp16 or bf16) is QUANTIZED on the way in with the descales
+    ``k_descale`` / ``v_descale`` (fp32 [B, Hkv], a Python float, or None = 1.0): ``byte = e4m3_rne(clamp(x /
+    descale, -448, 448))``, x the rotated key already rounded to k's dtype (V: the input). It needs a 16-byte
+    aligned cache with strides that are multiples of 16 and D a multiple of 16."""
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        b, hkv = cache_seqlens.size(0), k_cache.size(1)
+        return torch.ops.flash_attention.kvcache_append_fp8(
+            k_cache, v_cache, k, v, cache_seqlens, block_table, None, rotary_cos, rotary_sin,
+            _descale_arg(k_descale, "k_descale", b, hkv, k_cache.device),
+            _descale_arg(v_descale, "v_descale", b, hkv, k_cache.device))[0]
     return torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table, None,
                                                     rotary_cos, rotary_sin)[0]
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
                             cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
-                            return_seqlens=False):
+                            return_seqlens=False, k_descale=None, v_descale=None):
     """flash-attn's ``flash_attn_with_kvcache`` in this project's [B, H, S, D] layout: one serving step on
     a paged (``block_table`` given) or dense KV cache. When ``k`` / ``v`` [B, Hkv, Sn, D] are given they are
     appended in place at ``cache_seqlens`` (``flash_attn_kvcache_append``: the same drop rules); when the
@@ -573,7 +596,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     over ``[0, new_seqlens)`` without. Returns the attention output, or ``(out, new_seqlens)`` with
     ``return_seqlens=True``; ``cache_seqlens`` (required, int32 [B]) is not modified -- the caller copies
     ``new_seqlens`` into it (``cache_seqlens.copy_(new_seqlens)``) or takes them from
-    ``flash_attn_kvcache_append``. No host synchronisation (graph-capturable)."""
+    ``flash_attn_kvcache_append``. No host synchronisation (graph-capturable).
+
+    With FP8 caches (``torch.float8_e4m3fn``) and the descales ``k_descale`` / ``v_descale`` (fp32 [B, Hkv], a
+    Python float, or None = 1.0) the append quantizes and the FP8 paged kernel reads the bytes in place. A
+    dense FP8 cache [B, Hkv, Smax, D] is read by the same kernel through an identity table (batch row b is
+    page b, ``page_size = Smax``), so ``Smax`` must be a multiple of 32 (``ValueError`` otherwise): there
+    is no FP8 variant of the padded prefill kernel."""
     if cache_seqlens is None:
         raise ValueError("flash_attn_with_kvcache needs cache_seqlens (int32 [batch])")
     if (k is None) != (v is None):
@@ -582,6 +611,26 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         raise ValueError("rotary_cos and rotary_sin must be given together")
     softmax_scale = _default_scale(q, softmax_scale)
     new_seqlens, q_rot = cache_seqlens, q
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        b, hkv = q.size(0), k_cache.size(1)
+        if block_table is None and k_cache.size(2) % 32 != 0:
+            raise ValueError(f"a dense fp8 cache is read through the paged kernel: its length ({k_cache.size(2)}) "
+                             "must be a multiple of 32")
+        kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
+        vd = _descale_arg(v_descale, "v_descale", b, hkv, q.device)
+        if rotary_cos is not None:
+            new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append_fp8(
+                k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos.to(q.dtype), rotary_sin.to(q.dtype),
+                kd, vd)
+        elif k is not None:
+            new_seqlens, _ = torch.ops.flash_attention.kvcache_append_fp8(
+                k_cache, v_cache, k, v, cache_seqlens, block_table, None, None, None, kd, vd)
+        table = block_table
+        if table is None:  # a dense cache: batch row b is page b
+            table = torch.arange(b, dtype=torch.int32, device=q.device)[:, None]
+        out = torch.ops.flash_attention.paged_forward_fp8(q_rot, k_cache, v_cache, table, new_seqlens, kd, vd,
+                                                          softmax_scale, causal)
+        return (out, new_seqlens) if return_seqlens else out
     if rotary_cos is not None:  # (cast as apply_rope casts its tables)
         new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append(
             k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos.to(q.dtype), rotary_sin.to(q.dtype))
@@ -593,3 +642,172 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         out = flash_attn_padded_func(q_rot, k_cache, v_cache, torch.zeros_like(new_seqlens), new_seqlens,
                                      softmax_scale=softmax_scale, causal=causal)
     return (out, new_seqlens) if return_seqlens else out
+
+
+# ---------------------------------------------------------------------------------------------
+# FP8 (OCP e4m3, torch.float8_e4m3fn) KV cache -- a quantizing append and an in-place paged decode
+# (include/fa_gfx950_fp8.h); no reference counterpart (its README lists quantized types as a TODO). The
+# cache format of vLLM-style engines and of flash-attn's k_descale / v_descale. Scales are DESCALES: fp32,
+# positive, one per (batch row, kv-head); q and the output stay fp16 / bf16.
+#   read:   out = v_descale[b,h] * softmax((softmax_scale * k_descale[b,h]) * q . T(K8)^T) . T(V8)
+#   write:  byte = e4m3_rne(clamp(fp32(x) / descale[b,h], -448, 448))
+# ---------------------------------------------------------------------------------------------
+FP8_DTYPE = torch.float8_e4m3fn
+FP8_MAX = 448.0
+_FP8_UNSUPPORTED = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz")
+                         if hasattr(torch, n))
+
+
+def _is_fp8_cache(k_cache, v_cache, k_descale, v_descale) -> bool:
+    """Whether the caches are the FP8 format the kernels serve; the wrappers' dtype errors."""
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache and v_cache must have the same data type (got {k_cache.dtype} and {v_cache.dtype})")
+    if k_cache.dtype in _FP8_UNSUPPORTED:
+        raise ValueError(f"an 8-bit KV cache must be torch.float8_e4m3fn (OCP e4m3), not {k_cache.dtype}")
+    fp8 = k_cache.dtype == FP8_DTYPE
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError(f"k_descale / v_descale go with a torch.float8_e4m3fn cache, not {k_cache.dtype}")
+    return fp8
+
+
+def _descale_arg(x, name, batch, heads_kv, device):
+    """None, a Python number (expanded, stride 0) or an fp32 tensor broadcastable to [B, Hkv] on ``device``."""
+    if x is None:
+        return None
+    if isinstance(x, (int, float)):
+        return torch.full((1, 1), float(x), dtype=torch.float32, device=device).expand(batch, heads_kv)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise ValueError(f"{name} must be an fp32 tensor [batch, kv heads], a Python float or None")
+    if x.device != torch.device(device):
+        raise ValueError(f"{name} must be on {device} (got {x.device})")
+    try:
+        return x.expand(batch, heads_kv)
+    except RuntimeError as e:
+        raise ValueError(f"{name} must be [batch, kv heads] = [{batch}, {heads_kv}] (got {tuple(x.shape)})") from e
+
+
+def quantize_e4m3(x: torch.Tensor, descale) -> torch.Tensor:
+    """``e4m3_rne(clamp(fp32(x) / descale, -448, 448))``: the write formula (descale broadcasts against x)."""
+    return (x.float() / descale).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+
+
+def _descale_or_ones(x, batch, heads_kv, device):
+    return torch.ones(batch, heads_kv, dtype=torch.float32, device=device) if x is None else x.to(torch.float32)
+
+
+@torch.library.custom_op("flash_attention::paged_forward_fp8", mutates_args=())
+def flash_attention_paged_forward_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                      block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                      k_descale: Optional[torch.Tensor] = None,
+                                      v_descale: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                      causal: bool = False) -> torch.Tensor:
+    # Non-GPU default: dequantize and reuse paged_forward's default, in fp32 so that folding the per-(b, h)
+    # descales into q and the output rounds nothing
+    b, hkv = q.size(0), k_cache.size(1)
+    g = q.size(1) // hkv
+    kd = _descale_or_ones(k_descale, b, hkv, q.device).repeat_interleave(g, dim=1)[:, :, None, None]
+    vd = _descale_or_ones(v_descale, b, hkv, q.device).repeat_interleave(g, dim=1)[:, :, None, None]
+    scale = q.size(-1) ** -0.5 if softmax_scale is None else softmax_scale
+    out = flash_attention_paged_forward(q.float() * kd, k_cache.float(), v_cache.float(), block_table, cache_seqlens,
+                                        scale, causal)
+    return (out * vd).to(q.dtype)
+
+
+@torch.library.register_kernel("flash_attention::paged_forward_fp8", "cuda")
+def flash_attention_paged_forward_fp8_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                           block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                           k_descale: Optional[torch.Tensor] = None,
+                                           v_descale: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                           causal: bool = False) -> torch.Tensor:
+    _require_ext()
+    hkv = k_cache.size(1)
+    g, sq = q.size(1) // hkv, q.size(2)
+    if g * sq > _PAGED_DECODE_MAX_ROWS:
+        # the copying path of paged_forward: gather the bytes, widen them to q's dtype (exact), fold k_descale
+        # into the widened K (one more rounding of K, in q's dtype) and v_descale into the output
+        k = _gather_pages(k_cache.view(torch.uint8), block_table).view(FP8_DTYPE).to(q.dtype)
+        v = _gather_pages(v_cache.view(torch.uint8), block_table).view(FP8_DTYPE).to(q.dtype)
+        if k_descale is not None:
+            k = k * k_descale[:, :, None, None].to(q.dtype)
+        out = flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None, None,
+                                                  softmax_scale, causal, -1)
+        if v_descale is not None:
+            out = (out.float() * v_descale.repeat_interleave(g, dim=1)[:, :, None, None]).to(q.dtype)
+        return out
+    # the pool is read in place, never padded or copied: the library rejects D % 16 != 0 and misaligned pools
+    return flash_attention_cuda.flash_attention_paged_fp8_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), k_cache, v_cache, block_table, cache_seqlens, k_descale,
+        v_descale, softmax_scale, causal)
+
+
+@torch.library.register_fake("flash_attention::paged_forward_fp8")
+def flash_attention_paged_forward_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, k_descale=None,
+                                           v_descale=None, softmax_scale=None, causal=False):
+    return torch.empty_like(q)
+
+
+def _io_dtype(k, q):
+    """The 16-bit dtype of an fp8 append's inputs (q_rot's dtype; fp16 when there is neither k nor q)."""
+    return k.dtype if k is not None else q.dtype if q is not None else torch.float16
+
+
+@torch.library.custom_op("flash_attention::kvcache_append_fp8", mutates_args=("k_cache", "v_cache"))
+def flash_attention_kvcache_append_fp8(k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
+                                       v: Optional[torch.Tensor], cache_seqlens: torch.Tensor,
+                                       block_table: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                                       rotary_cos: Optional[torch.Tensor] = None,
+                                       rotary_sin: Optional[torch.Tensor] = None,
+                                       k_descale: Optional[torch.Tensor] = None,
+                                       v_descale: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    # Non-GPU default: kvcache_append's default on 16-bit scratch caches (placement, drop rules, rotation
+    # and rounding to the input dtype are its own), then the rows it wrote are quantized into the fp8 caches.
+    # A second run with each sequence's number as the "key" tells which sequence wrote which row.
+    dt = _io_dtype(k, q)
+    k16 = torch.zeros(k_cache.shape, dtype=dt, device=k_cache.device)
+    v16 = torch.zeros(v_cache.shape, dtype=dt, device=v_cache.device)
+    new_seqlens, q_rot = flash_attention_kvcache_append(k16, v16, k, v, cache_seqlens, block_table, q, rotary_cos,
+                                                        rotary_sin)
+    if k is not None and k.size(2) > 0:
+        b, hkv = k.size(0), k.size(1)
+        mark = torch.zeros(*k_cache.shape[:3], 1, dtype=torch.float32, device=k_cache.device)
+        ids = torch.arange(1, b + 1, dtype=torch.float32, device=k.device)[:, None, None, None].expand(
+            b, hkv, k.size(2), 1)
+        flash_attention_kvcache_append(mark, torch.zeros_like(mark), ids, ids, cache_seqlens, block_table)
+        owner = mark[..., 0].to(torch.int64) - 1  # [pages, Hkv, rows]: the sequence that wrote the row, or -1
+        written = owner >= 0
+        head = torch.arange(hkv, device=k_cache.device)[None, :, None].expand_as(owner)
+        for cache, x16, ds in ((k_cache, k16, k_descale), (v_cache, v16, v_descale)):
+            d = _descale_or_ones(ds, b, hkv, k_cache.device)[owner.clamp(min=0), head]  # [pages, Hkv, rows]
+            # (through byte views: index_put_ is not implemented for float8 tensors)
+            cache.view(torch.uint8)[written] = quantize_e4m3(x16[written], d[written][:, None]).view(torch.uint8)
+    return new_seqlens, q_rot
+
+
+@torch.library.register_kernel("flash_attention::kvcache_append_fp8", "cuda")
+def flash_attention_kvcache_append_fp8_cuda(k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor],
+                                            v: Optional[torch.Tensor], cache_seqlens: torch.Tensor,
+                                            block_table: Optional[torch.Tensor] = None,
+                                            q: Optional[torch.Tensor] = None,
+                                            rotary_cos: Optional[torch.Tensor] = None,
+                                            rotary_sin: Optional[torch.Tensor] = None,
+                                            k_descale: Optional[torch.Tensor] = None,
+                                            v_descale: Optional[torch.Tensor] = None
+                                            ) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    # as kvcache_append: inputs may be copied, the caches never (the binding rejects a cache whose last
+    # dimension is not contiguous, the library one that is not 16-byte aligned)
+    k, v, q = (t.contiguous() if t is not None and t.stride(3) != 1 else t for t in (k, v, q))
+    if rotary_cos is not None:
+        dt = _io_dtype(k, q)
+        rotary_cos, rotary_sin = rotary_cos.to(dt), rotary_sin.to(dt)
+    new_seqlens, q_rot = flash_attention_cuda.flash_attention_kvcache_append_fp8(
+        k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin, k_descale, v_descale)
+    return new_seqlens, q_rot
+
+
+@torch.library.register_fake("flash_attention::kvcache_append_fp8")
+def flash_attention_kvcache_append_fp8_fake(k_cache, v_cache, k, v, cache_seqlens, block_table=None, q=None,
+                                            rotary_cos=None, rotary_sin=None, k_descale=None, v_descale=None):
+    q_rot = (torch.empty(0, dtype=_io_dtype(k, q), device=k_cache.device) if q is None
+             else torch.empty(q.shape, dtype=q.dtype, device=q.device))
+    return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format), q_rot
