@@ -32,6 +32,10 @@ from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond th
     flash_attention_kvcache_append_fp8,
     flash_attention_paged_forward_fp8,
 )
+from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond the reference: windowed paged decode)
+    flash_attention_paged_window_forward,
+    flash_attention_paged_window_forward_fp8,
+)
 
 from .load_cpp_extention import load_extension  # noqa: F401  (the reference module imports it, :2)
 

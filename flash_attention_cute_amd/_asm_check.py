@@ -397,6 +397,12 @@ def check_file(path) -> list[str]:
         if "fa_decode_fp8kv" not in text:
             return [f"{path}: no fa_decode_fp8kv kernel in the assembly (stale or wrong file)"]
         return spills(text)
+    for inst, kernel in (("fa_paged_window_inst", "fa_decode_paged_window"),  # (the sliding-window variants)
+                         ("fa_paged_fp8_window_inst", "fa_decode_fp8kv_window")):
+        if inst in str(path):
+            if kernel not in text:
+                return [f"{path}: no {kernel} kernel in the assembly (stale or wrong file)"]
+            return spills(text)
     if "fa_fwd_w4" not in text:
         return [f"{path}: no fa_fwd_w4 kernel in the assembly (stale or wrong file)"]
     return agpr_violations(text) + spills(text) + hazards(text)

@@ -1,19 +1,20 @@
-// fa_decode_body.inc -- the body of the fa_decode kernel (fa_decode.hpp), included inside the kernel's
-// braces by fa_decode (FA_DEC_PAGED 0) and by fa_decode_paged (fa_decode_paged.hpp, FA_DEC_PAGED 1, `a`
-// a PagedDecArgs). A textual include, not a shared function template: with FA_DEC_PAGED 0 the dense
-// kernel is token for token what it was, so its instantiations compile to the same code as before the
-// paged kernel existed. The paged variant differs only in where a tile's K / V descriptors point
-// (PagedKv) and in taking every sequence's key count from seqlens_k. FA_DEC_WINDOW 1 (with FA_DEC_PAGED 1,
-// `a` a PagedWinDecArgs: fa_decode_paged_window.hpp) adds the sliding window at compile time, again by
-// preprocessor blocks, so the unwindowed paged kernels keep their tokens too.
-    using G = Geo<kD>;
-    using DG = DecGeo<kD>;
+// fa_decode_fp8_body.inc -- the body of the fa_decode_fp8kv kernel (fa_decode_paged_fp8.hpp), included inside
+// the kernel's braces by fa_decode_fp8kv and, with FA_DEC_WINDOW 1 and `a` a PagedFp8WinDecArgs, by
+// fa_decode_fp8kv_window (fa_decode_paged_fp8_window.hpp). A textual include for the reason fa_decode_body.inc
+// is one: without FA_DEC_WINDOW the kernel is token for token what it was.
+    using G = Geo<kD>;  // the 16-bit Q image
+    using FG = Fp8Geo<kD>;
     constexpr int KS = G::kKSteps;
+    constexpr int KP = FG::kPairs;
     constexpr int DTL = G::kDTiles;
-    constexpr int RB = DG::RB;
-    constexpr int NP = DG::kPieces;
-    __shared__ __attribute__((aligned(1024))) char lds[DG::kLds];
-    __shared__ __attribute__((aligned(1024))) char qlds[kDecRows * RB];
+    constexpr int QRB = G::kRowBytes;
+    constexpr int RB = FG::RB;
+    constexpr int NP = FG::kPieces;
+    constexpr int R = kFp8Ring;
+    typedef const __attribute__((address_space(4))) float *scale_t;  // (constant space: scalar loads)
+    typedef const __attribute__((address_space(4))) int32_t *len_t;
+    __shared__ __attribute__((aligned(1024))) char lds[FG::kLds];
+    __shared__ __attribute__((aligned(1024))) char qlds[kDecRows * QRB];
     __shared__ float ml[kDecWaves][kDecRows][2];
     __shared__ uint32_t last_wg;
 
@@ -23,10 +24,7 @@
     const int r = lane & 31;
     const int h = lane >> 5;
 
-    // ---- work: (unit = (b, hkv, rb), split) ----------------------------------------------------
-    // fused merge (a.cnt): unit u's splits are the workgroups (u >> 3) * n_split + split of XCD u & 7
-    // (the hardware deals workgroups to XCDs by id mod 8), so the last one reads the others' partials
-    // through its own L2; the grid pads every XCD to the same count (the extra workgroups leave)
+    // ---- work: (unit = (b, hkv, rb), split), as fa_decode ---------------------------------------
     int split, unit;
     if constexpr (kFuse) {
         const int k = (int)(blockIdx.x >> 3);
@@ -40,22 +38,14 @@
     const int rb = unit % a.n_rb;
     const int hkv = (unit / a.n_rb) % (int)p.num_heads_kv;
     const int b = unit / (a.n_rb * (int)p.num_heads_kv);
-    const int Sq = (int)p.seqlen_q, D = (int)p.headdim;  // Sq: positions per q-head (row addressing)
-    const float sc = p.softmax_scale;
+    const int Sq = (int)p.seqlen_q, D = (int)p.headdim;
+    // the descales of this (batch row, kv-head): k folds into the softmax scale, v into the final 1 / l
+    const int64_t dso = (int64_t)b * a.descale_batch_stride + (int64_t)hkv * a.descale_head_stride;
+    const float kds = a.k_descale ? ((scale_t)a.k_descale)[dso] : 1.f;
+    const float vds = a.v_descale ? ((scale_t)a.v_descale)[dso] : 1.f;
+    const float sc = p.softmax_scale * kds;
     const float thr_raw = kRescaleThr / sc;
-    // this batch row's keys: positions [k0, k0 + Sk) (a padded batch's key range, DecArgs); else
-    // every key
-    // (clamped to [0, seqlen_kv]: out-of-range positions never address outside the K / V rows)
-    int k0 = 0, Sk = (int)p.seqlen_kv;
-#if FA_DEC_PAGED
-    Sk = min(max(a.seqlens_k[b], 0), Sk);  // (keys [0, seqlens_k[b]), clamped to the table's capacity)
-#else
-    if (a.k_lo) {
-        const int sk_all = Sk;
-        k0 = min(max(a.k_lo[b], 0), sk_all);
-        Sk = min(max(a.k_hi[b], k0), sk_all) - k0;
-    }
-#endif
+    const int Sk = min(max(((len_t)a.seqlens_k)[b], 0), (int)p.seqlen_kv);
     const int diag = Sk - Sq;
 
     // this lane's row
@@ -64,40 +54,25 @@
     const int pos = row_ok ? rg % Sq : 0;
     const int lim = (kCausal && row_ok) ? min(Sk - 1, pos + diag) : Sk - 1;  // last visible key
 
-    // ---- this wave's tiles: a contiguous quarter of the split --------------------------------
+    // ---- this wave's tiles: a contiguous quarter of the split's equal share of the sequence ------
     const int n_tiles = (Sk + kDecKeys - 1) / kDecKeys;
-    // splits of the plan's (maximum) length; with per-sequence key ranges every split takes an equal
-    // share of THIS sequence's tiles instead, so a short sequence leaves no split empty and a long
-    // one no split overfull
 #if FA_DEC_WINDOW
-    // sliding window (a.window_left >= 0): row m sees keys n >= lo = m + diag - window_left. The sequence's
-    // tiles start at the tile of row 0's bound -- pages wholly below it, and their table entries, are never
-    // read -- and the splits share [t_first, n_tiles). All of it scalar, from values loaded as scalars.
+    // sliding window (a.window_left >= 0), as fa_decode_body.inc: the tiles start at the tile of row 0's lower
+    // bound, the splits share [t_first, n_tiles); scalar arithmetic
     const int t_first = max(diag - a.window_left, 0) / kDecKeys;
     const int lo = pos + diag - a.window_left;         // this lane's first visible key
     const int lo_max = Sq - 1 + diag - a.window_left;  // the last row's: tiles that start below it are masked
     const int tps = (n_tiles - t_first + a.n_split - 1) / a.n_split;
     const int s_lo = min(t_first + split * tps, n_tiles), s_hi = min(s_lo + tps, n_tiles);
 #else
-#if FA_DEC_PAGED
     const int tps = (n_tiles + a.n_split - 1) / a.n_split;
-#else
-    const int tps = a.k_lo ? (n_tiles + a.n_split - 1) / a.n_split : a.tps;
-#endif
     const int s_lo = min(split * tps, n_tiles), s_hi = min(s_lo + tps, n_tiles);
 #endif
     const int per_wave = (s_hi - s_lo + kDecWaves - 1) / kDecWaves;
     const int t_lo = min(s_lo + wave * per_wave, s_hi), t_hi = min(t_lo + per_wave, s_hi);
 
     const int ks_ = (int)p.k_seqlen_stride, vs_ = (int)p.v_seqlen_stride;
-#if FA_DEC_PAGED
-    PagedKv pages(p, a, b, hkv, t_lo, t_hi);
-#else
-    const char *kb = (const char *)p.k_ptr +
-                     2 * ((int64_t)b * p.k_batch_stride + (int64_t)hkv * p.k_head_stride + (int64_t)k0 * ks_);
-    const char *vb = (const char *)p.v_ptr +
-                     2 * ((int64_t)b * p.v_batch_stride + (int64_t)hkv * p.v_head_stride + (int64_t)k0 * vs_);
-#endif
+    PagedKv8 pages(p, a, b, hkv, t_lo, t_hi);
 
     // ---- LDS-DMA source offsets (lane-linear destination, swizzle on the source) ---------------
     constexpr int ROWS_PER_PIECE = 1024 / RB;
@@ -106,53 +81,47 @@
     for (int n = 0; n < NP; ++n) {
         const int row = n * ROWS_PER_PIECE + (16 * lane) / RB;
         const int slot = ((16 * lane) % RB) / 16;
-        const int kch = G::k_off(row, slot) % RB / 16;
-        const int vch = G::v_off(row, slot) % RB / 16;
-        kvo[n] = (kExactD || kch * 8 < D) ? row * ks_ * 2 + 16 * kch : 0x7ffffff0;
-        vvo[n] = (kExactD || vch * 8 < D) ? row * vs_ * 2 + 16 * vch : 0x7ffffff0;
+        const int kch = FG::k_off(row, slot) % RB / 16;  // (the XOR swizzles are involutions)
+        const int vch = FG::v_off(row, slot) % RB / 16;
+        kvo[n] = (kExactD || kch * 16 < D) ? row * ks_ + 16 * kch : 0x7ffffff0;
+        vvo[n] = (kExactD || vch * 16 < D) ? row * vs_ + 16 * vch : 0x7ffffff0;
     }
-    char *ring = lds + wave * DG::kWaveLds;
+    char *ring = lds + wave * FG::kWaveLds;
     const uint32_t ring_u = lds_u32(ring);
     auto issue = [&](const int t) {
         const int key0 = t * kDecKeys;
         const int rows = min(Sk - key0, kDecKeys);
-        const uint32_t dst = ring_u + (t & 1) * DG::kSlot;
-#if FA_DEC_PAGED
+        const uint32_t dst = ring_u + (t & (R - 1)) * FG::kSlot;
         const char *kt, *vt;
         pages.tile(t, kt, vt);
-        const rsrc_t kr = make_rsrc(kt, slab_bytes(rows, ks_, D));
-        const rsrc_t vr = make_rsrc(vt, slab_bytes(rows, vs_, D));
-#else
-        const rsrc_t kr = make_rsrc(kb + 2 * (int64_t)key0 * ks_, slab_bytes(rows, ks_, D));
-        const rsrc_t vr = make_rsrc(vb + 2 * (int64_t)key0 * vs_, slab_bytes(rows, vs_, D));
-#endif
+        const rsrc_t kr = make_rsrc(kt, slab_bytes8(rows, ks_, D));
+        const rsrc_t vr = make_rsrc(vt, slab_bytes8(rows, vs_, D));
         if (a.flags & kDecNt) {
 #pragma unroll
             for (int n = 0; n < NP; ++n) dma_one_nt(kr, dst + n * 1024, kvo[n], n == 0);
 #pragma unroll
-            for (int n = 0; n < NP; ++n) dma_one_nt(vr, dst + DG::kTile + n * 1024, vvo[n], n == 0);
+            for (int n = 0; n < NP; ++n) dma_one_nt(vr, dst + FG::kTile + n * 1024, vvo[n], n == 0);
         } else {
 #pragma unroll
             for (int n = 0; n < NP; ++n) dma_one(kr, dst + n * 1024, kvo[n], n == 0);
 #pragma unroll
-            for (int n = 0; n < NP; ++n) dma_one(vr, dst + DG::kTile + n * 1024, vvo[n], n == 0);
+            for (int n = 0; n < NP; ++n) dma_one(vr, dst + FG::kTile + n * 1024, vvo[n], n == 0);
         }
     };
-    // ---- Q: the row block's 32 rows by LDS-DMA into a shared K-swizzled image -----------------
-    // (rows are scattered over q-heads / positions; a descriptor over the group's span bounds
-    // them, invalid rows and columns past D read 0). Issued before the K/V tiles so that the
-    // counted wait below retires it.
+    // ---- Q: the row block's 32 rows by LDS-DMA into a shared K-swizzled 16-bit image, as fa_decode ----
     {
+        constexpr int QROWS_PER_PIECE = 1024 / QRB;
+        constexpr int QPW = kDecRows * QRB / 1024 / kDecWaves;
         const int64_t qspan = ((int64_t)(a.g - 1) * p.q_head_stride + (int64_t)(Sq - 1) * p.q_seqlen_stride + D) * 2;
         const rsrc_t qr = make_rsrc((const char *)p.q_ptr + 2 * ((int64_t)b * p.q_batch_stride +
                                                                  (int64_t)hkv * a.g * p.q_head_stride),
                                     (uint32_t)qspan);
 #pragma unroll
-        for (int n = 0; n < DG::kQPiecesPerWave; ++n) {
-            const int piece = wave * DG::kQPiecesPerWave + n;
-            const int row = piece * ROWS_PER_PIECE + (16 * lane) / RB;
-            const int slot = ((16 * lane) % RB) / 16;
-            const int ch = G::k_off(row, slot) % RB / 16;
+        for (int n = 0; n < QPW; ++n) {
+            const int piece = wave * QPW + n;
+            const int row = piece * QROWS_PER_PIECE + (16 * lane) / QRB;
+            const int slot = ((16 * lane) % QRB) / 16;
+            const int ch = G::k_off(row, slot) % QRB / 16;
             const int rq = rb * kDecRows + row;
             const int off = (rq < a.rows && (kExactD || ch * 8 < D))
                                 ? 2 * ((rq / Sq) * (int)p.q_head_stride + (rq % Sq) * (int)p.q_seqlen_stride) + 16 * ch
@@ -160,27 +129,28 @@
             dma_one(qr, lds_u32(qlds) + piece * 1024, off, n == 0);
         }
     }
-    const bool has0 = t_lo < t_hi, has1 = t_lo + 1 < t_hi;
-    if (has0) issue(t_lo);
-    if (has1) issue(t_lo + 1);
-    if (has1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * NP) : "memory");
-    else if (has0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the ring's first tiles; the counted wait retires the Q pieces (issued first) and leaves them in flight
+    const int n_pre = min(t_hi - t_lo, R);
+    for (int i = 0; i < n_pre; ++i) issue(t_lo + i);
+    wait_tiles<2 * NP>(n_pre);
     __syncthreads();  // every wave's Q pieces landed
-    // B operand of S^T = K.Q^T: lane (h, r) holds Q[row r][16 ks + 8 h .. +7]
+    // B operand of S^T = K.Q^T in K's d order: lane (h, r) holds Q[row r][32 j + 16 h + 8 e .. + 7] for
+    // k-step 2 j + e
     u32x4 qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const u32x4 *)(qlds + G::k_off(r, 2 * ks + h));
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const u32x4 *)(qlds + G::k_off(r, 4 * (ks >> 1) + 2 * h + (ks & 1)));
 
-    // ---- per-lane LDS fragment addresses (fa_fwd_w8 layouts) ----------------------------------
-    const int g4 = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
+    // ---- per-lane LDS fragment addresses --------------------------------------------------------
     int v_addr[DTL];
+    {
+        const int g4 = lane >> 4, q = (lane >> 1) & 7, pp = lane & 1;
+        const int row0 = 4 * (g4 >> 1) + (q & 3) + 8 * (q >> 2);
 #pragma unroll
-    for (int dt = 0; dt < DTL; ++dt)
-        v_addr[dt] = G::v_off(4 * (g4 >> 1) + qq, dt * 4 + 2 * (g4 & 1) + (pp >> 1)) + 8 * (pp & 1);
-    int k_addr[KS];
+        for (int dt = 0; dt < DTL; ++dt) v_addr[dt] = FG::v_off(row0, 2 * dt + (g4 & 1)) + 8 * pp;
+    }
+    int k_addr[KP];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) k_addr[ks] = G::k_off(r, 2 * ks + h);
+    for (int j = 0; j < KP; ++j) k_addr[j] = FG::k_off(r, 2 * j + h);
 
     f32x16 o[DTL];
 #pragma unroll
@@ -188,38 +158,33 @@
     float m_use = kNeg, msc = 0.f, l_run = 0.f;
 
     for (int t = t_lo; t < t_hi; ++t) {
-        // tile t landed (the youngest 2*NP pieces, tile t+1, may still be in flight)
-        if (t + 1 < t_hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NP) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const char *K = ring + (t & 1) * DG::kSlot;
-        const char *V = K + DG::kTile;
-        u32x4 kf[KS];
+        // tile t landed (the younger tiles of the ring may still be in flight)
+        wait_tiles<2 * NP>(min(t_hi - 1 - t, R - 1));
+        const char *K = ring + (t & (R - 1)) * FG::kSlot;
+        const char *V = K + FG::kTile;
+        u32x4 k8[KP];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kf[ks] = *(const u32x4 *)(K + k_addr[ks]);
-        u32x4 va[2][DTL];
+        for (int j = 0; j < KP; ++j) k8[j] = *(const u32x4 *)(K + k_addr[j]);
+        u32x2 v8[2][DTL];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-            for (int dt = 0; dt < DTL; ++dt) {
-                const u32x2 lo = tr_read(V + kk * 16 * RB + v_addr[dt]);
-                const u32x2 hi = tr_read(V + kk * 16 * RB + 8 * RB + v_addr[dt]);
-                va[kk][dt] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-            }
-        // the slot is free once its fragments are in registers: refill it with tile t+2
+            for (int dt = 0; dt < DTL; ++dt) v8[kk][dt] = tr8_read(V + kk * 16 * RB + v_addr[dt]);
+        // the slot is free once its bytes are in registers: refill it with tile t + R
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (t + 2 < t_hi) issue(t + 2);
+        if (t + R < t_hi) issue(t + R);
 
         f32x16 s = {};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s = DT::mfma(kf[ks], qf[ks], s);
+        for (int j = 0; j < KP; ++j) {
+            s = DT::mfma(widen8<DT>(k8[j][0], k8[j][1]), qf[2 * j], s);
+            s = DT::mfma(widen8<DT>(k8[j][2], k8[j][3]), qf[2 * j + 1], s);
+        }
 
         const int key0 = t * kDecKeys;
         // lane (h, r) holds keys key0 + (i & 3) + 8 (i >> 2) + 4 h of row r
 #if FA_DEC_WINDOW
-        // (the window's lower bound joins the mask: only a sequence's first one or two tiles enter for it.
-        // A row whose window starts in a later tile than row 0's sees an all-masked tile first: its m_use
-        // stays kNeg, msc 0, every exp2 underflows to 0 and alpha is 0 at its first visible key, so O and l
-        // stay 0 through it)
+        // (the window's lower bound joins the mask, as in fa_decode_body.inc)
         if (__builtin_amdgcn_ballot_w64(key0 + kDecKeys - 1 > lim) || key0 < lo_max) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -237,11 +202,9 @@
         float mx = fmaxf(s[0], s[1]);
 #pragma unroll
         for (int i = 2; i < 16; ++i) mx = fmaxf(mx, s[i]);
-        // both lane halves hold the same row's m_use: the check needs no cross-half reduction
         if (__builtin_amdgcn_ballot_w64(mx > m_use + thr_raw)) {
             const float m_new = fmaxf(m_use, pair_max(mx));
             const float msc_new = (m_new <= 0.5f * kNeg) ? 0.f : m_new * sc;
-            // a row's first visible key: O and l are still 0, alpha must not overflow
             const float alpha = (m_use <= 0.5f * kNeg) ? 0.f : __builtin_amdgcn_exp2f(msc - msc_new);
             m_use = m_new;
             msc = msc_new;
@@ -263,11 +226,11 @@
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-            for (int dt = 0; dt < DTL; ++dt) o[dt] = DT::mfma(va[kk][dt], pf[kk], o[dt]);
+            for (int dt = 0; dt < DTL; ++dt) o[dt] = DT::mfma(widen8<DT>(v8[kk][dt][0], v8[kk][dt][1]), pf[kk], o[dt]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- merge the 4 wave partials in LDS ------------------------------------------------------
+    // ---- merge the 4 wave partials in LDS (fa_decode's, with v_descale in the final 1 / l) --------
     __syncthreads();  // every wave is done with its ring
     float *ow = (float *)lds;  // [wave][row][kD]
     {
@@ -314,7 +277,7 @@
             acc[i + 3] += wgt[w] * x.w;
         }
     }
-    const float inv = L > 0.f ? 1.f / L : 0.f;
+    const float inv = L > 0.f ? vds / L : 0.f;
     const int rg2 = rb * kDecRows + row;
     if (a.n_split == 1) {
         if (rg2 < a.rows) {
@@ -342,9 +305,7 @@
             if (part == 0) a.ws_lse[slot] = L > 0.f ? M + __builtin_amdgcn_logf(L) : kNeg;  // log2
         }
         if constexpr (kFuse) {
-            // fused merge: every thread's partials are in L2 before the workgroup arrives; the last
-            // arrival merges the unit (the others' stores were drained before their arrivals, and
-            // its loads bypass its CU's L1)
+            // fused merge, as fa_decode: the last arrival of the unit merges its splits' partials
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (tid == 0) {

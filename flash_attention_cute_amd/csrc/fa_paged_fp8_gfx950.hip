@@ -39,32 +39,10 @@ int check_paged_fp8(const fa_paged_fp8_params *v, int dtype, int causal) {
     return fa_fwd_gfx950_paged_check(&v->paged, dtype, causal);
 }
 
-// The split plan: decode_plan's rule (every wave at least kDecMinTilesPerWave tiles, at most kDecMaxSplit
-// splits) aiming at kFp8DecTargetWgs workgroups instead of kDecTargetWgs. A workgroup streams half the bytes
-// per key here, and the measured optimum moves from "fewer, longer splits" to one workgroup per CU: B1 Hkv8
-// 131072 keys, same process, 0.0814 / 0.0635 / 0.0555 / 0.0486 / 0.0484 ms at 96 / 128 / 160 / 192 / 256
-// workgroups (profiles/fp8_decode_target_ab.json). A dec_target knob that was moved off its default wins.
-constexpr int64_t kFp8DecTargetWgs = 256;
-
-fa::DecArgs fp8_decode_plan(const fa_fwd_params &p, int max_split) {
-    fa::DecArgs a = fa::decode_plan(p, max_split);
-    if (fa::knobs().dec_target != fa::kDecTargetWgs) return a;
-    const int64_t units = fa::decode_units(p, a);
-    const int n_tiles = (int)((p.seqlen_kv + fa::kDecKeys - 1) / fa::kDecKeys);
-    int64_t ns = (kFp8DecTargetWgs + units - 1) / units;
-    const int64_t by_len = n_tiles / (fa::kDecWaves * fa::kDecMinTilesPerWave);
-    ns = ns < by_len ? ns : by_len;
-    ns = ns < max_split ? ns : max_split;
-    ns = ns < 1 ? 1 : ns;
-    a.tps = (int)((n_tiles + ns - 1) / ns);
-    a.n_split = (n_tiles + a.tps - 1) / a.tps;
-    return a;
-}
-
 fa::PagedFp8DecArgs paged_fp8_plan(const fa_paged_fp8_params *v, bool split) {
     fa::PagedFp8DecArgs a{};
     const fa_paged_params &g = v->paged;
-    static_cast<fa::DecArgs &>(a) = fp8_decode_plan(g.base, split ? fa::kDecMaxSplit : 1);
+    static_cast<fa::DecArgs &>(a) = fa::fp8_decode_plan(g.base, split ? fa::kDecMaxSplit : 1);
     a.block_table = g.block_table;
     a.block_table_stride = g.block_table_stride;
     a.seqlens_k = g.seqlens_k;

@@ -31,6 +31,7 @@
 #include "fa_gfx950_fp8.h"
 #include "fa_gfx950_kvcache.h"
 #include "fa_gfx950_paged.h"
+#include "fa_gfx950_paged_window.h"
 
 namespace flash_attention {
 
@@ -531,6 +532,11 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // fp8 (flash_attention_paged_fp8_fwd, include/fa_gfx950_fp8.h fa_fwd_gfx950_paged_fp8): the caches are
 // torch.float8_e4m3fn pools read in place (never copied: 16-byte aligned, strides multiples of 16), q / o
 // stay fp16 / bf16, k_descale / v_descale are fp32 [B, Hkv] device tensors of any strides (undefined: 1.0).
+//
+// window (flash_attention_paged_window_fwd / _fp8_fwd, include/fa_gfx950_paged_window.h): window_left >= 0
+// goes to the windowed entries WITHOUT the q-head pack -- the window is relative to the real Sq, so a decode
+// step is passed as Sq 1 with g q-heads per kv-head (the same kernel rows and arithmetic as the pack, causal
+// dropped as the pack drops it); window_left < 0 is the unwindowed call, to the letter.
 struct Fp8Descales {
     const torch::Tensor *k, *v;  // nullptr / undefined tensor: 1.0
 };
@@ -564,7 +570,7 @@ void fill_descales(const Fp8Descales &ds, const torch::Tensor &like, int64_t bs,
 
 torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
                              torch::Tensor &block_table, torch::Tensor &cache_seqlens, float softmax_scale,
-                             bool causal, const Fp8Descales *fp8) {
+                             bool causal, const Fp8Descales *fp8, int64_t window_left = -1) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
                 "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
     TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
@@ -602,8 +608,9 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     torch::Tensor vx = fp8 ? v_cache : aligned_or_contiguous(v_cache);
     torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
     torch::Tensor sl = cache_seqlens.contiguous();
+    const bool window = window_left >= 0;
     if (qx.size(2) == 1) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
-        qx = pack_head_q(qx, kx.size(1));
+        if (!window) qx = pack_head_q(qx, kx.size(1));
         causal = false;
     }
     auto o = alloc_out_like(qx);
@@ -628,11 +635,29 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
         torch::Tensor keep_k, keep_v;
         fill_descales(*fp8, q, bs, kx.size(1), fp.k_descale, fp.v_descale, fp.descale_batch_stride,
                       fp.descale_head_stride, keep_k, keep_v);
+        if (window) {
+            const int64_t ws_bytes = fa_fwd_gfx950_paged_window_fp8_workspace_size(&fp, dtype, causal ? 1 : 0, window_left);
+            TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_window_fp8_workspace_size failed: ", fa_last_error());
+            torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+            check_rc(fa_fwd_gfx950_paged_window_fp8(&fp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
+                                                    current_stream(qx)),
+                     "fa_fwd_gfx950_paged_window_fp8");
+            return shaped_like(o, q);
+        }
         const int64_t ws_bytes = fa_fwd_gfx950_paged_fp8_workspace_size(&fp, dtype, causal ? 1 : 0);
         TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_fp8_workspace_size failed: ", fa_last_error());
         torch::Tensor ws = workspace_for(ws_bytes, qx.options());
         check_rc(fa_fwd_gfx950_paged_fp8(&fp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
                  "fa_fwd_gfx950_paged_fp8");
+        return shaped_like(o, q);
+    }
+    if (window) {
+        const int64_t ws_bytes = fa_fwd_gfx950_paged_window_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
+        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_window_workspace_size failed: ", fa_last_error());
+        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+        check_rc(fa_fwd_gfx950_paged_window(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
+                                            current_stream(qx)),
+                 "fa_fwd_gfx950_paged_window");
         return shaped_like(o, q);
     }
     const int64_t ws_bytes = fa_fwd_gfx950_paged_workspace_size(&pp, dtype, causal ? 1 : 0);
@@ -655,6 +680,21 @@ torch::Tensor flash_attention_paged_fp8_fwd(torch::Tensor &q, torch::Tensor &k_c
                                             c10::optional<torch::Tensor> v_descale, float softmax_scale, bool causal) {
     const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds);
+}
+
+torch::Tensor flash_attention_paged_window_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                               torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                               int64_t window_left, float softmax_scale, bool causal) {
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, nullptr, window_left);
+}
+
+torch::Tensor flash_attention_paged_window_fp8_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                                   torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                                   int64_t window_left, c10::optional<torch::Tensor> k_descale,
+                                                   c10::optional<torch::Tensor> v_descale, float softmax_scale,
+                                                   bool causal) {
+    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds, window_left);
 }
 
 // In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
@@ -876,4 +916,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_kvcache_append_fp8", &flash_attention::flash_attention_kvcache_append_fp8,
           "Quantizing in-place append to an FP8 (e4m3) KV cache with fused rotate-half RoPE, one HIP launch (gfx950)");
     m.def("fp8_version", []() { return fa_fp8_version(); });
+    m.def("flash_attention_paged_window_fwd", &flash_attention::flash_attention_paged_window_fwd,
+          "Sliding-window decode over a paged KV cache: pages below the window are never read, gfx950");
+    m.def("flash_attention_paged_window_fp8_fwd", &flash_attention::flash_attention_paged_window_fp8_fwd,
+          "Sliding-window decode over a paged FP8 (e4m3) KV cache read in place, gfx950");
+    m.def("paged_window_version", []() { return fa_paged_window_version(); });
 }

@@ -403,6 +403,13 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
     # of the sequence's pages + torch SDPA with the kernel's semantics (bottom-right causal per sequence,
     # GQA, rows with no visible key 0, lengths clamped to the table's capacity).
     warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, -1)
+
+
+def _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, window_left):
+    """The non-GPU default of the paged ops. With a window (``window_left >= 0``, ``_window_mask`` per
+    sequence) the pages wholly below the sequence's first visible key are not gathered, as the kernel never
+    reads them or their table entries."""
     out = torch.zeros_like(q)
     sq = q.size(2)
     num_pages, _, page_size, _ = k_cache.shape
@@ -411,10 +418,15 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
         n = min(max(n, 0), cap)
         if n == 0:
             continue
-        ids = block_table[b, :(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
-        kb = k_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
-        vb = v_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n]
-        mask = _bottom_right_causal(sq, n, q.device) if causal else None
+        first = max(0, n - sq - window_left) // page_size if window_left >= 0 else 0  # the first page read
+        k0 = first * page_size
+        ids = block_table[b, first:(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
+        kb = k_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n - k0]
+        vb = v_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n - k0]
+        if window_left >= 0:
+            mask = _window_mask(sq, n, window_left, causal, q.device)[:, k0:]
+        else:
+            mask = _bottom_right_causal(sq, n, q.device) if causal else None
         out[b:b + 1] = _masked_sdpa(q[b:b + 1], kb, vb, mask, softmax_scale)
     return out
 
@@ -423,17 +435,24 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
 def flash_attention_paged_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                                        block_table: torch.Tensor, cache_seqlens: torch.Tensor,
                                        softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    return _paged_cuda(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, -1)
+
+
+def _paged_cuda(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, window_left):
     _require_ext()
     g, sq = q.size(1) // k_cache.size(1), q.size(2)
     if g * sq > _PAGED_DECODE_MAX_ROWS:
         # the copying path: the kernel serves decode shapes only, larger query blocks (a chunked prefill
-        # on a paged cache) gather the table's pages into a dense cache for the padded entry. No host
-        # synchronisation either, so it stays graph-capturable.
+        # on a paged cache) gather the table's pages into a dense cache for the padded entry (with the
+        # window, if any). No host synchronisation either, so it stays graph-capturable.
         k = _gather_pages(k_cache, block_table)
         v = _gather_pages(v_cache, block_table)
         return flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None,
-                                                   None, softmax_scale, causal, -1)
+                                                   None, softmax_scale, causal, window_left)
     # (a head dim that is no multiple of 8 pads the pool: a copy of it)
+    if window_left >= 0:
+        return _padded_call(flash_attention_cuda.flash_attention_paged_window_fwd, (q, k_cache, v_cache), block_table,
+                            cache_seqlens, int(window_left), softmax_scale, causal)
     return _padded_call(flash_attention_cuda.flash_attention_paged_fwd, (q, k_cache, v_cache), block_table,
                         cache_seqlens, softmax_scale, causal)
 
@@ -444,8 +463,39 @@ def flash_attention_paged_forward_fake(q, k_cache, v_cache, block_table, cache_s
     return torch.empty_like(q)
 
 
+# Sliding window over the paged cache (include/fa_gfx950_paged_window.h fa_fwd_gfx950_paged_window): ops of
+# their own beside paged_forward / paged_forward_fp8, whose schemas stay as they are.
+_MAX_WINDOW = 2 ** 30  # (the library clamps a larger window to this; it covers any capacity)
+
+
+@torch.library.custom_op("flash_attention::paged_window_forward", mutates_args=())
+def flash_attention_paged_window_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                         block_table: torch.Tensor, cache_seqlens: torch.Tensor, window_left: int,
+                                         softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    # paged_forward where query m of sequence b sees only keys n >= m + L_b - Sq - window_left
+    # (window_left < 0: no window). Non-GPU default: paged_forward's, under _window_mask per sequence.
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal,
+                            min(int(window_left), _MAX_WINDOW))
+
+
+@torch.library.register_kernel("flash_attention::paged_window_forward", "cuda")
+def flash_attention_paged_window_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                              block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                              window_left: int, softmax_scale: float = None,
+                                              causal: bool = False) -> torch.Tensor:
+    return _paged_cuda(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal,
+                       min(int(window_left), _MAX_WINDOW))
+
+
+@torch.library.register_fake("flash_attention::paged_window_forward")
+def flash_attention_paged_window_forward_fake(q, k_cache, v_cache, block_table, cache_seqlens, window_left,
+                                              softmax_scale=None, causal=False):
+    return torch.empty_like(q)
+
+
 def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False,
-                          k_descale=None, v_descale=None):
+                          k_descale=None, v_descale=None, window_left=-1):
     """Attention of q [B, Hq, Sq, D] -- each sequence's LAST Sq positions -- over a paged KV cache:
     ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] with any strides (flash-attn's
     [num_pages, page_size, Hkv, D] is ``cache.transpose(1, 2)``), ``page_size`` a multiple of 32;
@@ -464,13 +514,31 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     fp16 / bf16) is read in place by the FP8 paged kernel with the descales ``k_descale`` / ``v_descale``
     (fp32 [B, Hkv] on q's device, any strides; a Python float is expanded; None is 1.0): ``out = v_descale *
     softmax(softmax_scale * k_descale * q . K8^T) . V8`` with the bytes widened exactly. Its copying path
-    multiplies the widened K by ``k_descale`` in q's dtype, which rounds K once more."""
+    multiplies the widened K by ``k_descale`` in q's dtype, which rounds K once more.
+
+    ``window_left >= 0`` is a sliding window, per sequence, on either cache format: with ``L_b`` the clamped
+    length, query m sees only keys ``n >= m + L_b - Sq - window_left`` (and ``n <= m + L_b - Sq`` with
+    ``causal``): ``window_left + 1`` keys ending at the diagonal, flash-attn's ``window_size=(window_left,
+    ...)``, transformers' ``sliding_window - 1``. The decode kernel then reads only the 32-key tiles from
+    ``max(0, L_b - Sq - window_left) // 32`` on: PAGES WHOLLY BELOW THAT TILE, AND THEIR TABLE ENTRIES, ARE
+    NEVER READ, so an engine may free them and leave anything in the entries; its splits are planned for the
+    window, not the cache. The copying path passes the window to ``flash_attn_padded_func`` (it gathers every
+    page of the table, so there the entries of freed pages must still be valid to clamp). ``window_left < 0``
+    (the default) is no window: the call above, bit for bit."""
     softmax_scale = _default_scale(q, softmax_scale)
+    window_left = int(window_left)
     if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
         b, hkv = q.size(0), k_cache.size(1)
-        return torch.ops.flash_attention.paged_forward_fp8(
-            q, k_cache, v_cache, block_table, cache_seqlens, _descale_arg(k_descale, "k_descale", b, hkv, q.device),
-            _descale_arg(v_descale, "v_descale", b, hkv, q.device), softmax_scale, causal)
+        kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
+        vd = _descale_arg(v_descale, "v_descale", b, hkv, q.device)
+        if window_left >= 0:
+            return torch.ops.flash_attention.paged_window_forward_fp8(q, k_cache, v_cache, block_table, cache_seqlens,
+                                                                      window_left, kd, vd, softmax_scale, causal)
+        return torch.ops.flash_attention.paged_forward_fp8(q, k_cache, v_cache, block_table, cache_seqlens, kd, vd,
+                                                           softmax_scale, causal)
+    if window_left >= 0:
+        return torch.ops.flash_attention.paged_window_forward(q, k_cache, v_cache, block_table, cache_seqlens,
+                                                              window_left, softmax_scale, causal)
     return torch.ops.flash_attention.paged_forward(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale,
                                                    causal)
 
@@ -586,7 +654,7 @@ def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
                             cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
-                            return_seqlens=False, k_descale=None, v_descale=None):
+                            return_seqlens=False, k_descale=None, v_descale=None, window_left=-1):
     """flash-attn's ``flash_attn_with_kvcache`` in this project's [B, H, S, D] layout: one serving step on
     a paged (``block_table`` given) or dense KV cache. When ``k`` / ``v`` [B, Hkv, Sn, D] are given they are
     appended in place at ``cache_seqlens`` (``flash_attn_kvcache_append``: the same drop rules); when the
@@ -602,7 +670,15 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     Python float, or None = 1.0) the append quantizes and the FP8 paged kernel reads the bytes in place. A
     dense FP8 cache [B, Hkv, Smax, D] is read by the same kernel through an identity table (batch row b is
     page b, ``page_size = Smax``), so ``Smax`` must be a multiple of 32 (``ValueError`` otherwise): there
-    is no FP8 variant of the padded prefill kernel."""
+    is no FP8 variant of the padded prefill kernel.
+
+    ``window_left >= 0`` (flash-attn's ``window_size=(window_left, ...)``) windows the attention half as
+    ``flash_attn_paged_func(window_left=...)`` does; the append is unchanged. On a paged cache, and on a dense
+    FP8 cache through its identity table, the windowed paged kernel never reads the pages below the window. On
+    a dense 16-bit cache a decode step (``Sq == 1``) folds the window into its key range on the device,
+    ``[max(new_seqlens - 1 - window_left, 0), new_seqlens)``, and runs the split-KV decode kernel; ``Sq > 1``
+    passes the window to ``flash_attn_padded_func``. Still no host synchronisation."""
+    window_left = int(window_left)
     if cache_seqlens is None:
         raise ValueError("flash_attn_with_kvcache needs cache_seqlens (int32 [batch])")
     if (k is None) != (v is None):
@@ -628,8 +704,12 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         table = block_table
         if table is None:  # a dense cache: batch row b is page b
             table = torch.arange(b, dtype=torch.int32, device=q.device)[:, None]
-        out = torch.ops.flash_attention.paged_forward_fp8(q_rot, k_cache, v_cache, table, new_seqlens, kd, vd,
-                                                          softmax_scale, causal)
+        if window_left >= 0:
+            out = torch.ops.flash_attention.paged_window_forward_fp8(q_rot, k_cache, v_cache, table, new_seqlens,
+                                                                     window_left, kd, vd, softmax_scale, causal)
+        else:
+            out = torch.ops.flash_attention.paged_forward_fp8(q_rot, k_cache, v_cache, table, new_seqlens, kd, vd,
+                                                              softmax_scale, causal)
         return (out, new_seqlens) if return_seqlens else out
     if rotary_cos is not None:  # (cast as apply_rope casts its tables)
         new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append(
@@ -637,10 +717,16 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     elif k is not None:
         new_seqlens, _ = torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table)
     if block_table is not None:
-        out = flash_attn_paged_func(q_rot, k_cache, v_cache, block_table, new_seqlens, softmax_scale, causal)
+        out = flash_attn_paged_func(q_rot, k_cache, v_cache, block_table, new_seqlens, softmax_scale, causal,
+                                    window_left=window_left)
+    elif window_left >= 0 and q.size(2) == 1:
+        # one query row: its window IS a key range (no row-dependent bound), so the padded decode kernel serves it
+        k_start = (new_seqlens - 1 - min(window_left, _MAX_WINDOW)).clamp(min=0)
+        out = flash_attn_padded_func(q_rot, k_cache, v_cache, k_start, new_seqlens, softmax_scale=softmax_scale,
+                                     causal=causal)
     else:
         out = flash_attn_padded_func(q_rot, k_cache, v_cache, torch.zeros_like(new_seqlens), new_seqlens,
-                                     softmax_scale=softmax_scale, causal=causal)
+                                     softmax_scale=softmax_scale, causal=causal, window_left=window_left)
     return (out, new_seqlens) if return_seqlens else out
 
 
@@ -703,13 +789,20 @@ def flash_attention_paged_forward_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_
                                       causal: bool = False) -> torch.Tensor:
     # Non-GPU default: dequantize and reuse paged_forward's default, in fp32 so that folding the per-(b, h)
     # descales into q and the output rounds nothing
+    return _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale,
+                                causal, -1)
+
+
+def _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale, causal,
+                         window_left):
     b, hkv = q.size(0), k_cache.size(1)
     g = q.size(1) // hkv
     kd = _descale_or_ones(k_descale, b, hkv, q.device).repeat_interleave(g, dim=1)[:, :, None, None]
     vd = _descale_or_ones(v_descale, b, hkv, q.device).repeat_interleave(g, dim=1)[:, :, None, None]
     scale = q.size(-1) ** -0.5 if softmax_scale is None else softmax_scale
-    out = flash_attention_paged_forward(q.float() * kd, k_cache.float(), v_cache.float(), block_table, cache_seqlens,
-                                        scale, causal)
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=3)
+    out = _paged_reference(q.float() * kd, k_cache.float(), v_cache.float(), block_table, cache_seqlens, scale, causal,
+                           window_left)
     return (out * vd).to(q.dtype)
 
 
@@ -719,6 +812,12 @@ def flash_attention_paged_forward_fp8_cuda(q: torch.Tensor, k_cache: torch.Tenso
                                            k_descale: Optional[torch.Tensor] = None,
                                            v_descale: Optional[torch.Tensor] = None, softmax_scale: float = None,
                                            causal: bool = False) -> torch.Tensor:
+    return _paged_fp8_cuda(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale, causal,
+                           -1)
+
+
+def _paged_fp8_cuda(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale, causal,
+                    window_left):
     _require_ext()
     hkv = k_cache.size(1)
     g, sq = q.size(1) // hkv, q.size(2)
@@ -730,11 +829,15 @@ def flash_attention_paged_forward_fp8_cuda(q: torch.Tensor, k_cache: torch.Tenso
         if k_descale is not None:
             k = k * k_descale[:, :, None, None].to(q.dtype)
         out = flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None, None,
-                                                  softmax_scale, causal, -1)
+                                                  softmax_scale, causal, window_left)
         if v_descale is not None:
             out = (out.float() * v_descale.repeat_interleave(g, dim=1)[:, :, None, None]).to(q.dtype)
         return out
     # the pool is read in place, never padded or copied: the library rejects D % 16 != 0 and misaligned pools
+    if window_left >= 0:
+        return flash_attention_cuda.flash_attention_paged_window_fp8_fwd(
+            q if q.stride(-1) == 1 else q.contiguous(), k_cache, v_cache, block_table, cache_seqlens, int(window_left),
+            k_descale, v_descale, softmax_scale, causal)
     return flash_attention_cuda.flash_attention_paged_fp8_fwd(
         q if q.stride(-1) == 1 else q.contiguous(), k_cache, v_cache, block_table, cache_seqlens, k_descale,
         v_descale, softmax_scale, causal)
@@ -743,6 +846,33 @@ def flash_attention_paged_forward_fp8_cuda(q: torch.Tensor, k_cache: torch.Tenso
 @torch.library.register_fake("flash_attention::paged_forward_fp8")
 def flash_attention_paged_forward_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, k_descale=None,
                                            v_descale=None, softmax_scale=None, causal=False):
+    return torch.empty_like(q)
+
+
+@torch.library.custom_op("flash_attention::paged_window_forward_fp8", mutates_args=())
+def flash_attention_paged_window_forward_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                             block_table: torch.Tensor, cache_seqlens: torch.Tensor, window_left: int,
+                                             k_descale: Optional[torch.Tensor] = None,
+                                             v_descale: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                             causal: bool = False) -> torch.Tensor:
+    # paged_forward_fp8 under the sliding window of paged_window_forward (window_left < 0: no window)
+    return _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale,
+                                causal, min(int(window_left), _MAX_WINDOW))
+
+
+@torch.library.register_kernel("flash_attention::paged_window_forward_fp8", "cuda")
+def flash_attention_paged_window_forward_fp8_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                                  block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                                  window_left: int, k_descale: Optional[torch.Tensor] = None,
+                                                  v_descale: Optional[torch.Tensor] = None,
+                                                  softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    return _paged_fp8_cuda(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale, causal,
+                           min(int(window_left), _MAX_WINDOW))
+
+
+@torch.library.register_fake("flash_attention::paged_window_forward_fp8")
+def flash_attention_paged_window_forward_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, window_left,
+                                                  k_descale=None, v_descale=None, softmax_scale=None, causal=False):
     return torch.empty_like(q)
 
 
