@@ -19,6 +19,9 @@ import sys
 QBASE, QEND = 128, 192  # the Q fragments a128..a191 belong to the inline asm (fa_agpr_asm.inc)
 _REG = re.compile(r"\ba\[(\d+)(?::\d+)?\]|\ba(\d+)\b")
 _TILE = re.compile(r"ELi(64|128)ELb")  # the head-dim tile template argument of the mangled name
+# fa_fwd_w4 and its paged variant fa_fwd_w4_paged (csrc/fa_paged_prefill.hpp: the same body, the same pinned
+# AGPRs and hand-placed waits): both take every fa_fwd_w4 rule
+_W4 = ("_ZN2fa9fa_fwd_w4", "_ZN2fa15fa_fwd_w4_paged")
 
 
 def pinned_p8(fn: str, reg: int) -> bool:
@@ -43,7 +46,7 @@ def agpr_violations(text: str) -> list[str]:
     for ln in text.splitlines():
         m = re.match(r"^(_Z\S*):", ln)
         if m:
-            fn = m.group(1) if m.group(1).startswith(("_ZN2fa9fa_fwd_w4", "_ZN2fa9fa_fwd_p8")) else None
+            fn = m.group(1) if m.group(1).startswith((*_W4, "_ZN2fa9fa_fwd_p8")) else None
             continue
         if ";;#ASMSTART" in ln:
             in_asm = True
@@ -122,7 +125,7 @@ def _parse(text: str):
     for ln in text.splitlines():
         m = re.match(r"^(_Z\S*):", ln)
         if m:
-            fn = m.group(1) if m.group(1).startswith("_ZN2fa9fa_fwd_w4") else None
+            fn = m.group(1) if m.group(1).startswith(_W4) else None
             if fn:
                 kernels[fn] = []
             continue
@@ -403,6 +406,8 @@ def check_file(path) -> list[str]:
             if kernel not in text:
                 return [f"{path}: no {kernel} kernel in the assembly (stale or wrong file)"]
             return spills(text)
+    if "fa_paged_prefill_inst" in str(path) and "fa_fwd_w4_paged" not in text:  # (then every fa_fwd_w4 rule)
+        return [f"{path}: no fa_fwd_w4_paged kernel in the assembly (stale or wrong file)"]
     if "fa_fwd_w4" not in text:
         return [f"{path}: no fa_fwd_w4 kernel in the assembly (stale or wrong file)"]
     return agpr_violations(text) + spills(text) + hazards(text)

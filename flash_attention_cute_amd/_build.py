@@ -9,12 +9,13 @@ into the package directory so the artefacts travel with the repository snapshot.
      head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_paged_inst.hip x 16 (the
      paged decode kernels, the same combinations) + csrc/fa_paged_fp8_inst.hip x 16 (the FP8 paged decode
      kernels) + csrc/fa_paged_window_inst.hip x 16 and csrc/fa_paged_fp8_window_inst.hip x 16 (their
-     sliding-window variants) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip, csrc/fa_paged_fp8_gfx950.hip,
-     csrc/fa_paged_window_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip (stand-alone kernels with
+     sliding-window variants) + csrc/fa_paged_prefill_inst.hip x 16 (the paged fa_fwd_w4) + csrc/fa_fwd_gfx950.hip,
+     csrc/fa_paged_gfx950.hip, csrc/fa_paged_fp8_gfx950.hip, csrc/fa_paged_window_gfx950.hip,
+     csrc/fa_paged_prefill_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip (stand-alone kernels with
      their entries)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
-     include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h and include/fa_gfx950_paged_window.h; no torch
-     symbols)
+     include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h and
+     include/fa_gfx950_paged_prefill.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -180,7 +181,10 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     # the sliding-window variants of the paged and FP8 paged decode kernels (csrc/fa_paged_window_inst.hip,
     # csrc/fa_paged_fp8_window_inst.hip), the same combinations, in directories that none of the patterns above
     # match: the unwindowed instantiations compile exactly as without them
-    for prefix, name in (("win", "fa_paged_window_inst"), ("win8", "fa_paged_fp8_window_inst")):
+    # and the paged variant of fa_fwd_w4 (csrc/fa_paged_prefill_inst.hip, the paged prefill), the same way: the
+    # dense fa_inst objects compile exactly as without it, and its assembly takes the whole fa_fwd_w4 gate
+    for prefix, name in (("win", "fa_paged_window_inst"), ("win8", "fa_paged_fp8_window_inst"),
+                         ("pfill", "fa_paged_prefill_inst")):
         win_deps = fp8_deps + [CSRC / f"{name}.hip"]
         for dt, c, d, e in INSTANCES:
             idir = objdir / f"{prefix}_{dt.lower()}_c{c}_d{d}_x{e}"
@@ -196,7 +200,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     # C-ABI dispatchers (dense, paged, FP8 paged, sliding-window paged), standalone RoPE kernel, KV-cache append
     # kernels
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_fp8_gfx950.hip", "fa_paged_window_gfx950.hip",
-                "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip"):
+                "fa_paged_prefill_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src, "-o", obj], obj,
@@ -207,7 +211,8 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         line = " ".join(map(str, cmd))
         if (not force and not _stale(obj, deps) and stamp.exists() and stamp.read_text() == line
                 and (obj.name not in ("fa_inst.o", "fa_paged_inst.o", "fa_paged_fp8_inst.o", "fa_paged_window_inst.o",
-                                     "fa_paged_fp8_window_inst.o") or next(obj.parent.glob("*.s"), None) is not None)):
+                                     "fa_paged_fp8_window_inst.o", "fa_paged_prefill_inst.o")
+                     or next(obj.parent.glob("*.s"), None) is not None)):
             return
         _run(cmd, verbose)
         stamp.write_text(line)

@@ -77,6 +77,7 @@ def lib(debug: bool = False) -> ctypes.CDLL:
         lib.fa_debug_set_dec_fuse.argtypes = [ctypes.c_int]
         lib.fa_debug_set_dec_fuse.restype = None
         lib.fa_debug_last_zigzag.restype = ctypes.c_int
+        lib.fa_debug_last_prefill_paged.restype = ctypes.c_int
         lib.fa_split_errors.argtypes = [ctypes.c_int]
         lib.fa_split_errors.restype = ctypes.c_int64
         lib.fa_debug_set_xccs.argtypes = [ctypes.c_int]
@@ -134,6 +135,12 @@ def set_zigzag(mode: int | None = None, debug: bool = False) -> None:
 def last_zigzag(debug: bool = False) -> bool:
     """Whether the last prefill launch on this thread ran zigzag Q blocks."""
     return lib(debug).fa_debug_last_zigzag() == 1
+
+
+def last_prefill_paged(debug: bool = False) -> bool:
+    """Whether the last prefill launch on this thread read K / V in place through a block table (the paged
+    fa_fwd_w4, whose ``last_path()`` is "w4" as well); any other prefill launch resets it."""
+    return lib(debug).fa_debug_last_prefill_paged() == 1
 
 
 def set_split(mode: int | None = None, debug: bool = False) -> None:

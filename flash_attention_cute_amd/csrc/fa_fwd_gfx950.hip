@@ -152,7 +152,18 @@ namespace {
 thread_local int g_last_zigzag = 0;
 }
 extern "C" int fa_debug_last_zigzag(void) { return g_last_zigzag; }
-void fa::set_last_zigzag(int z) { g_last_zigzag = z; }
+// fa_debug_last_prefill_paged: 1 when the last prefill launch on this thread read K / V through a block table
+// (fa_fwd_gfx950_paged_prefill; its fa_debug_last_path is w4, the kernel it is). Every prefill launch records its
+// layout through set_last_zigzag, which resets the flag; the paged launch sets it afterwards.
+namespace {
+thread_local int g_last_prefill_paged = 0;
+}
+extern "C" int fa_debug_last_prefill_paged(void) { return g_last_prefill_paged; }
+void fa::set_last_prefill_paged(bool paged) { g_last_prefill_paged = paged ? 1 : 0; }
+void fa::set_last_zigzag(int z) {
+    g_last_zigzag = z;
+    g_last_prefill_paged = 0;
+}
 
 unsigned long long *fa::stamp_buffer() { return g_stamps; }
 

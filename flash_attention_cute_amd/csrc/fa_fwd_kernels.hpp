@@ -881,6 +881,72 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 // 7, lgkmcnt 15)
 constexpr int vmcnt_enc(int n) { return (n & 15) | (((n >> 4) & 3) << 14) | 0x70 | 0xF00; }
 
+// FA_W4_PAGED (fa_paged_prefill.hpp sets it to 1 before including this file; every other translation unit
+// leaves it 0 and preprocesses to what it was): the kernel below is named fa_fwd_w4_paged, takes a
+// PagedPrefillArgs and reads K / V tiles through a block table.
+#ifndef FA_W4_PAGED
+#define FA_W4_PAGED 0
+#endif
+#if FA_W4_PAGED
+// Where the K / V tiles of one Q block of sequence b live. A page holds tpp whole 64-key tiles, so tile t is
+// tile t % tpp of page row[t / tpp]. The pipelined loop issues K tile j + 1 and V tile j in iteration j --
+// across a page boundary they sit in different pages -- so there are two cursors: `k` for the next K tile and
+// `v`, one tile behind it, which takes over k's page when it crosses. Page ids are scalar loads through the
+// constant address space: the id of page pi + 1 is fetched when k ENTERS page pi (one page ahead of its use,
+// at least a tile of MFMA / softmax work), and only while pi + 1 <= pi_last, the page of the block's last tile
+// (n_end - 1) -- so a table row is never indexed outside [j_lo / tpp, (n_end - 1) / tpp], which lies below
+// ceil(L_b / page_size) <= max_pages. The K tile the loop prefetches past the block's last tile keeps the last
+// id (a causal block's tile n_end: staged, never used) or gets an empty descriptor (a tile past L_b): neither is
+// a table read. An id is clamped into the pool, so a bad entry never addresses outside it; the page term is
+// 64-bit (a pool holds more than 2^31 elements); rows past the sequence end are cut by the caller's
+// descriptor bound, never read from the page.
+struct PagedTiles {
+    typedef const __attribute__((address_space(4))) int32_t *table_t;  // (constant space: a scalar load)
+    const char *kh, *vh;  // the pool at this kv-head
+    int64_t kps, vps;     // page strides, bytes
+    int64_t kts, vts;     // tile strides within a page, bytes
+    table_t row;          // this sequence's block-table row
+    int tpp, last_page, pi_last;
+    int pi, k_tip, k_id, next_id;  // cursor k: its page index in the row, tile within the page, page id; the next page's
+    int v_tip, v_id;               // cursor v
+
+    __device__ __forceinline__ int64_t clamped(const int id) const { return min(max(id, 0), last_page); }
+    // one page id, fetched now: tile t of the row (the block's first tile, staged outside the tile loop)
+    __device__ __forceinline__ void at(const int t, const char *&k, const char *&v) const {
+        const int p0 = t / tpp;
+        const int64_t page = clamped(row[p0]);
+        k = kh + page * kps + (t - p0 * tpp) * kts;
+        v = vh + page * vps + (t - p0 * tpp) * vts;
+    }
+    // cursor v at tile j0, cursor k at tile j0 + 1, of a block whose tiles are [j0, n_end); n_end <= j0 reads
+    // no entry
+    __device__ __forceinline__ void start(const int j0, const int n_end) {
+        pi_last = n_end > 0 ? (n_end - 1) / tpp : 0;
+        pi = j0 / tpp;
+        k_tip = j0 - pi * tpp;
+        k_id = next_id = 0;
+        if (j0 < n_end) {
+            k_id = row[pi];
+            if (pi < pi_last) next_id = row[pi + 1];
+        }
+        advance();
+    }
+    // both cursors one tile on
+    __device__ __forceinline__ void advance() {
+        v_tip = k_tip;
+        v_id = k_id;
+        if (++k_tip == tpp) {
+            k_tip = 0;
+            ++pi;
+            k_id = next_id;
+            if (pi < pi_last) next_id = row[pi + 1];
+        }
+    }
+    __device__ __forceinline__ const char *k() const { return kh + clamped(k_id) * kps + k_tip * kts; }
+    __device__ __forceinline__ const char *v() const { return vh + clamped(v_id) * vps + v_tip * vts; }
+};
+#endif
+
 // =============================================================================================
 // fa_fwd_w4: one wave per SIMD, 64 query rows per wave (two 32-row blocks A and B). Per KV tile j:
 //
@@ -899,8 +965,14 @@ constexpr int vmcnt_enc(int n) { return (n & 15) | (((n >> 4) & 3) << 14) | 0x70
 // has been drained.
 // =============================================================================================
 template <class DT, bool kCausal, int kD, bool kExactD>
+#if FA_W4_PAGED
+__global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
+                                                          unsigned long long *stamps, const PathArgs xa,
+                                                          const PagedPrefillArgs pg) {
+#else
 __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const int n_qtiles, const int dbg,
                                                     unsigned long long *stamps, const PathArgs xa) {
+#endif
     // Diagnostic build only (-DFA_STAMPS=1, scripts/stamps.py): per-wave s_memtime phase totals.
 #ifdef FA_STAMPS
     // (32-bit cycle stamps: a block's deltas fit, and half the SGPRs of 64-bit ones keep the
@@ -1012,7 +1084,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // but the causal diagonal of a block is ONE tile instead of four (plain 256-row blocks: 4 masked
     // tiles, 2 of them A-dead), and no tile is A-dead. Units: (batch, q-head quad u) rows of n_qtiles
     // (the host passes Sq / 64 q-tiles); g / 4 quads share a K/V stream.
+#if FA_W4_PAGED  // (plain blocks only, known at compile time: no head-packed, key-split or zigzag state to carry)
+    constexpr bool hp = false;
+#else
     const bool hp = kCausal && xa.head_pack != 0;
+#endif
     const int heads_u = hp ? (int)p.num_heads_q / 4 : (int)p.num_heads_q;             // head rows of the work order
     const int grp_u = hp ? (int)p.head_q_per_group / 4 : (int)p.head_q_per_group;  // of them per K/V stream
     const uint32_t nwg = (uint32_t)n_qtiles * (uint32_t)heads_u * (uint32_t)p.batch_size;
@@ -1025,7 +1101,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // neighbouring workgroups, in one pass: workgroup 2u runs tiles [mid, n_end) of the heavy q-tile,
     // workgroup 2u + 1 its tiles [0, mid) and then the light q-tile whole, with mid putting the same
     // work on both (a block switch and the hand-off counted as FA_PAIR_SHIFT tiles).
+#if FA_W4_PAGED
+    constexpr bool spl = false;
+#else
     const bool spl = kCausal && xa.split_ws != nullptr;
+#endif
     const bool pairs = spl && xa.split_pairs != 0;
     const int nqp = n_qtiles >> 1;  // (key-split launches: the host passes twice the plain q-tiles)
     const uint32_t nunits = pairs ? (uint32_t)((nqp + 1) >> 1) * (uint32_t)heads_u * p.batch_size : spl ? nwg >> 1 : nwg;
@@ -1101,7 +1181,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // the heaviest of the 256-row blocks setting the span (the C4 rank share at N = 8: 256 blocks on
     // 256 CUs). Block A's rows are always the workgroup's first 128 rows from m0 (the A-dead tiles
     // below follow); block B's rows start rowB rows after block A's (128 for the plain layout).
+#if FA_W4_PAGED
+    constexpr bool zz = false;
+#else
     const bool zz = kCausal && xa.zigzag;
+#endif
     // Key-split causal blocks (xa.split_ws, dense causal launches whose blocks fit one round; the host
     // passes twice the q-tiles): item 2t + k is piece k of plain q-tile t, over the first (k = 0) or
     // second (k = 1) half of the block's key tiles. Both pieces of a q-tile are heavy-first
@@ -1135,6 +1219,15 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // tiles below j_um have a score left of some row's window (masked like the diagonal)
     const int wl = xa.window_left;
     int j_lo = 0, j_um = 0;
+#if FA_W4_PAGED
+    PagedTiles pt;  // (set_block: the row and the kv-head; the block prologue: the cursors)
+    pt.kps = 2 * p.k_batch_stride;
+    pt.vps = 2 * p.v_batch_stride;
+    pt.kts = 2 * (int64_t)kBlockN * p.k_seqlen_stride;
+    pt.vts = 2 * (int64_t)kBlockN * p.v_seqlen_stride;
+    pt.tpp = pg.tiles_per_page;
+    pt.last_page = pg.num_pages - 1;
+#endif
     auto set_block = [&](const Work wk) {
         const int hq = hp ? 4 * wk.hq + wave : wk.hq, b = wk.b;  // (hp: wk.hq is the q-head quad)
         const int hkv = hq / (int)p.head_q_per_group;
@@ -1152,6 +1245,17 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
             krow0 = (int64_t)k0 * p.k_seqlen_stride;
             vrow0 = (int64_t)k0 * p.v_seqlen_stride;
         }
+#if FA_W4_PAGED
+        {   // this sequence's keys: its length clamped to the table's capacity (p.seqlen_kv), its tiles through
+            // its block-table row (kb / vb below: the pool at this kv-head; the batch stride is the PAGE stride)
+            const int bu = __builtin_amdgcn_readfirstlane(b);
+            Sk = min(max(((PagedTiles::table_t)pg.seqlens_k)[bu], 0), (int)p.seqlen_kv);
+            diag = Sk - Sq;
+            n_blocks = (Sk + kBlockN - 1) / kBlockN;
+            krow0 = vrow0 = 0;
+            pt.row = (PagedTiles::table_t)(pg.block_table + (int64_t)bu * pg.block_table_stride);
+        }
+#endif
         if (kExactD && xa.cos) {  // (RoPE: dense launches of exact-D instantiations only)
             const int64_t crow0 = (int64_t)b * xa.batch_stride;
             cosb = (const char *)xa.cos + 2 * crow0;
@@ -1161,6 +1265,10 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
         kb = (const char *)p.k_ptr + 2 * (krow0 + (int64_t)hkv * p.k_head_stride);
         vb = (const char *)p.v_ptr + 2 * (vrow0 + (int64_t)hkv * p.v_head_stride);
         ob = (char *)p.o_ptr + 2 * (orow0 + (int64_t)hq * p.o_head_stride);
+#if FA_W4_PAGED
+        pt.kh = kb;
+        pt.vh = vb;
+#endif
         geom_of(qtile_of(wk), Sq, m0, rowB);
         // rows interleaved over the waves: block A = rows mw..mw+31 (the workgroup's first half),
         // block B = rows mw+rowB.. (its second half), so the last causal diagonal tiles hold no
@@ -1323,6 +1431,24 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     }
     // tile j into ring slot `slot` (the block's tiles alternate slots from j_lo on), outside the
     // pipelined loop: every piece names M0 as an input (hipcc sets it; one wait state in the asm)
+#if FA_W4_PAGED
+    // (paged: tile j's page id is fetched here, from the row set_block chose -- under the previous block's
+    // drain that is the NEXT block's row and length; a block without tiles, j >= n_end, reads no entry and
+    // stages an empty descriptor)
+    auto stage_pieces = [&](const bool is_k, const int stride, const int j, const uint32_t m0v, const int *voff) {
+        const char *kt = pt.kh, *vt = pt.vh;
+        const bool live = j < n_end;
+        if (live) pt.at(j, kt, vt);
+        dma_tile<NP>(make_rsrc_u(is_k ? kt : vt, live ? slab_bytes(min(Sk - j * kBlockN, kBlockN), stride, D) : 0u),
+                     m0v, voff);
+    };
+    auto stage_k = [&](const int j, const int slot) {
+        stage_pieces(true, ks_, j, lds_u32(lds + KV0 + slot * T) + wave * NP * 1024, kvo);
+    };
+    auto stage_v = [&](const int j, const int slot) {
+        stage_pieces(false, vs_, j, lds_u32(lds + KV0 + (2 + slot) * T) + wave * NP * 1024, vvo);
+    };
+#else
     auto stage_pieces = [&](const char *base, const int stride, const int j, const uint32_t m0v, const int *voff) {
         const int key0 = j * kBlockN;
         // (make_rsrc_u: the descriptor provably in SGPRs, whatever the register pressure)
@@ -1335,6 +1461,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     auto stage_v = [&](const int j, const int slot) {
         stage_pieces(vb, vs_, j, lds_u32(lds + KV0 + (2 + slot) * T) + wave * NP * 1024, vvo);
     };
+#endif
 
     // ---- per-lane LDS read addresses -----------------------------------------------------
     const int g = lane >> 4;
@@ -1827,8 +1954,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     for (int i = 0; i < 4; ++i) st_fa[i] = 0;
 #endif
 #endif
+#if FA_W4_PAGED
+    pt.start(j_lo, n_end);  // (its scalar loads retire under the wait for Q and K_0 below)
+#else
     kp = kb + (j_lo + 1) * step_k;
     vp = vb + j_lo * step_v;
+#endif
     kfe = Sk / kBlockN;
     k_last = tile_bytes(kfe * kBlockN, full_k, ks_);
     if (rope_q) load_q_rope();
@@ -1937,8 +2068,15 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
         }
         FA_STAMP(sa);
         // (unmasked: j + 1 <= n_pipe <= kfe, V_j full)
+#if FA_W4_PAGED
+        // (the same bounds over the cursors' tiles; make_rsrc_u: the ids come from memory)
+        const rsrc_t kq = make_rsrc_u(pt.k(), mk == 0 ? (j + 1 < kfe ? full_k : k_last) : tile_bytes((j + 1) * kBlockN, full_k, ks_));
+        const rsrc_t vq = make_rsrc_u(pt.v(), mk == 0 ? full_v : tile_bytes(j * kBlockN, full_v, vs_));
+        pt.advance();
+#else
         const rsrc_t kq = make_rsrc(kp, mk == 0 ? (j + 1 < kfe ? full_k : k_last) : tile_bytes((j + 1) * kBlockN, full_k, ks_));
         const rsrc_t vq = make_rsrc(vp, mk == 0 ? full_v : tile_bytes(j * kBlockN, full_v, vs_));
+#endif
         // FA_EXP_*: timing experiments of the stamps build only (results are garbage)
 #if defined(FA_EXP_NOSM)
         phase1(lds + KV0 + c * T, PAR, IC<0>{}, IC<1>{}, kq, vq, AD{});
@@ -1947,8 +2085,10 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
 #else
         phase1(lds + KV0 + c * T, PAR, IC<!first>{}, IC<1>{}, kq, vq, AD{});
 #endif
+#if !FA_W4_PAGED
         kp += step_k;
         vp += step_v;
+#endif
 #if FA_EPI_OVL
         if constexpr (first) {  // the previous block's O has been read: O = 0 for this block
             zero_o();
@@ -2471,6 +2611,7 @@ template <class DT, bool C, int kD, bool kExact>
 int launch_mb(const fa_fwd_params &p, hipStream_t stream, bool m16);
 #endif
 
+#if !FA_W4_PAGED  // (the paged kernel's launch: fa_paged_prefill.hpp)
 // ---- host launch of one instantiation -------------------------------------------------
 template <class DT, bool C, int kD, bool kExact>
 int launch_one(const fa_fwd_params &p, const PathArgs &xa, hipStream_t stream) {
@@ -2528,5 +2669,6 @@ int launch_one(const fa_fwd_params &p, const PathArgs &xa, hipStream_t stream) {
     set_last_zigzag(xz.split_ws ? (xz.head_pack ? 5 : 2) + xz.split_pairs : xz.head_pack ? 4 : xz.zigzag);
     return FA_OK;
 }
+#endif  // !FA_W4_PAGED
 
 }  // namespace fa

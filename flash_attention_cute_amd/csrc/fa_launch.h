@@ -67,7 +67,8 @@ inline int variant_from_env() { return knobs().variant; }
 enum Path { kPathNone = 0, kPathW4 = 1, kPathW8 = 2, kPathW4Slow = 3, kPathDecode = 4, kPathDecodeSplit = 5, kPathP8 = 6,
             kPathM32 = 7, kPathM16 = 8, kPathDecodePaged = 9, kPathDecodePagedSplit = 10 };
 void set_last_path(int path);
-void set_last_zigzag(int z);
+void set_last_zigzag(int z);  // (every prefill launch; resets fa_debug_last_prefill_paged)
+void set_last_prefill_paged(bool paged);  // (fa_debug_last_prefill_paged: the launch read K / V through a block table)
 void set_last_dec_fused(bool fused);  // (fa_debug_last_dec_fused: the last decode launch merged in-kernel)
 
 // diagnostic per-wave phase stamps of fa_fwd_w4 (only a -DFA_STAMPS=1 build writes them; see

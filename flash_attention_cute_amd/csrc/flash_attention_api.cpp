@@ -31,6 +31,7 @@
 #include "fa_gfx950_fp8.h"
 #include "fa_gfx950_kvcache.h"
 #include "fa_gfx950_paged.h"
+#include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_window.h"
 
 namespace flash_attention {
@@ -526,7 +527,8 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // caches page pools [num_pages, Hkv, page_size, D] (any strides, last dim contiguous; page_size a
 // multiple of 32), block_table int32 [B, max_pages], cache_seqlens int32 [B], both on the device. The
 // pool is read in place: no gather, no host synchronisation (graph-capturable). Decode shapes only
-// (g * Sq <= 64; the Python op gathers larger query blocks); Sq == 1 takes the q-head pack of
+// (g * Sq <= 64; larger query blocks: flash_attention_paged_prefill_fwd below, or the Python op's
+// copying path); Sq == 1 takes the q-head pack of
 // flash_attention_fwd. No reference counterpart.
 //
 // fp8 (flash_attention_paged_fp8_fwd, include/fa_gfx950_fp8.h fa_fwd_gfx950_paged_fp8): the caches are
@@ -570,7 +572,7 @@ void fill_descales(const Fp8Descales &ds, const torch::Tensor &like, int64_t bs,
 
 torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
                              torch::Tensor &block_table, torch::Tensor &cache_seqlens, float softmax_scale,
-                             bool causal, const Fp8Descales *fp8, int64_t window_left = -1) {
+                             bool causal, const Fp8Descales *fp8, int64_t window_left = -1, bool prefill = false) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
                 "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
     TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
@@ -609,7 +611,7 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
     torch::Tensor sl = cache_seqlens.contiguous();
     const bool window = window_left >= 0;
-    if (qx.size(2) == 1) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
+    if (qx.size(2) == 1 && !prefill) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
         if (!window) qx = pack_head_q(qx, kx.size(1));
         causal = false;
     }
@@ -631,6 +633,16 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     pp.seqlens_k = sl.data_ptr<int32_t>();
 
     const int dtype = fa_dtype(qx);
+    if (prefill) {  // (16-bit pools only: the Python op keeps FP8 pools on its copying path)
+        TORCH_CHECK(!fp8, "the paged prefill kernel reads 16-bit pools only");
+        const int64_t ws_bytes = fa_fwd_gfx950_paged_prefill_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
+        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_prefill_workspace_size failed: ", fa_last_error());
+        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+        check_rc(fa_fwd_gfx950_paged_prefill(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
+                                             current_stream(qx)),
+                 "fa_fwd_gfx950_paged_prefill");
+        return shaped_like(o, q);
+    }
     if (fp8) {
         torch::Tensor keep_k, keep_v;
         fill_descales(*fp8, q, bs, kx.size(1), fp.k_descale, fp.v_descale, fp.descale_batch_stride,
@@ -686,6 +698,16 @@ torch::Tensor flash_attention_paged_window_fwd(torch::Tensor &q, torch::Tensor &
                                                torch::Tensor &block_table, torch::Tensor &cache_seqlens,
                                                int64_t window_left, float softmax_scale, bool causal) {
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, nullptr, window_left);
+}
+
+// Prefill-sized query blocks over a 16-bit paged cache (include/fa_gfx950_paged_prefill.h
+// fa_fwd_gfx950_paged_prefill): the pool read in place by the paged fa_fwd_w4, page_size a multiple of 64, any
+// g * Sq (no q-head pack), window_left < 0 for no window. The Python op routes g * Sq > 64 here.
+torch::Tensor flash_attention_paged_prefill_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                                torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                                int64_t window_left, float softmax_scale, bool causal) {
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, nullptr, window_left,
+                          true);
 }
 
 torch::Tensor flash_attention_paged_window_fp8_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
@@ -921,4 +943,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_paged_window_fp8_fwd", &flash_attention::flash_attention_paged_window_fp8_fwd,
           "Sliding-window decode over a paged FP8 (e4m3) KV cache read in place, gfx950");
     m.def("paged_window_version", []() { return fa_paged_window_version(); });
+    m.def("flash_attention_paged_prefill_fwd", &flash_attention::flash_attention_paged_prefill_fwd,
+          "Prefill-sized query blocks over a 16-bit paged KV cache read in place (page_size % 64 == 0), gfx950");
+    m.def("paged_prefill_version", []() { return fa_paged_prefill_version(); });
 }

@@ -382,6 +382,7 @@ def flash_attn_window_func(q, k, v, window_left, softmax_scale=None, causal=Fals
 # block_table[b][n / page_size], and it has cache_seqlens[b] keys.
 # ---------------------------------------------------------------------------------------------
 _PAGED_DECODE_MAX_ROWS = 64  # csrc/fa_launch.h kDecMaxRows: (q-head, position) rows per kv-head
+_PAGED_PREFILL_TILE = 64  # csrc/fa_launch.h kBlockN: the paged prefill kernel's pages hold whole key tiles
 
 
 def _gather_pages(cache: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
@@ -442,9 +443,14 @@ def _paged_cuda(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, 
     _require_ext()
     g, sq = q.size(1) // k_cache.size(1), q.size(2)
     if g * sq > _PAGED_DECODE_MAX_ROWS:
-        # the copying path: the kernel serves decode shapes only, larger query blocks (a chunked prefill
-        # on a paged cache) gather the table's pages into a dense cache for the padded entry (with the
-        # window, if any). No host synchronisation either, so it stays graph-capturable.
+        # larger query blocks (a chunked prefill on a paged cache): the paged prefill kernel reads a 16-bit
+        # pool in place when a page holds whole 64-key tiles and the head dim needs no padding copy
+        if k_cache.size(2) % _PAGED_PREFILL_TILE == 0 and q.size(3) % 8 == 0:
+            return _padded_call(flash_attention_cuda.flash_attention_paged_prefill_fwd, (q, k_cache, v_cache),
+                                block_table, cache_seqlens, int(window_left), softmax_scale, causal)
+        # the copying path, for the other page sizes (32, 96, ...) and a padded head dim: the table's pages
+        # are gathered into a dense cache for the padded entry (with the window, if any). No host
+        # synchronisation either, so it stays graph-capturable.
         k = _gather_pages(k_cache, block_table)
         v = _gather_pages(v_cache, block_table)
         return flash_attention_padded_forward_cuda(q, k, v, torch.zeros_like(cache_seqlens), cache_seqlens, None,
@@ -506,9 +512,12 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     bottom-right aligned per sequence; a sequence without keys gives 0 rows.
 
     Decode shapes (``Hq / Hkv * Sq <= 64``) read the pool in place with the paged split-KV kernel. Larger
-    query blocks take the COPYING path: the table's pages are gathered into a dense cache
-    (``index_select``) for ``flash_attn_padded_func``. Neither path synchronises with the host, so both
-    can be captured in a graph.
+    query blocks (a prompt chunk over a cached prefix) read a 16-bit pool in place with the paged prefill
+    kernel when ``page_size`` is a multiple of 64 and D a multiple of 8, bit-identical to
+    ``flash_attn_padded_func`` on the gathered cache. They take the COPYING path -- the table's pages
+    gathered into a dense cache (``index_select``) for ``flash_attn_padded_func`` -- for FP8 pools, other
+    page sizes (32, 96, ...) and a padded head dim. No path synchronises with the host, so all can be
+    captured in a graph.
 
     An FP8 cache (``torch.float8_e4m3fn`` pools, 16-byte aligned, D a multiple of 16; q and the output stay
     fp16 / bf16) is read in place by the FP8 paged kernel with the descales ``k_descale`` / ``v_descale``
@@ -522,8 +531,10 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     ...)``, transformers' ``sliding_window - 1``. The decode kernel then reads only the 32-key tiles from
     ``max(0, L_b - Sq - window_left) // 32`` on: PAGES WHOLLY BELOW THAT TILE, AND THEIR TABLE ENTRIES, ARE
     NEVER READ, so an engine may free them and leave anything in the entries; its splits are planned for the
-    window, not the cache. The copying path passes the window to ``flash_attn_padded_func`` (it gathers every
-    page of the table, so there the entries of freed pages must still be valid to clamp). ``window_left < 0``
+    window, not the cache. The paged prefill kernel gives the same guarantee per 64-key tile (pages wholly
+    below ``max(0, L_b - Sq - window_left) // 64 * 64`` and their entries are never read). The copying path
+    passes the window to ``flash_attn_padded_func`` (it gathers every page of the table, so there the entries
+    of freed pages must still be valid to clamp). ``window_left < 0``
     (the default) is no window: the call above, bit for bit."""
     softmax_scale = _default_scale(q, softmax_scale)
     window_left = int(window_left)
