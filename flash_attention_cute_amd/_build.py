@@ -6,13 +6,11 @@ files into the source tree. Here nothing is hipified: two explicit compiler invo
 into the package directory so the artefacts travel with the repository snapshot.
 
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
-     head-dim tile x exact-D instantiation, compiled in parallel) + csrc/fa_paged_inst.hip x 16 (the
-     paged decode kernels, the same combinations) + csrc/fa_paged_fp8_inst.hip x 16 (the FP8 paged decode
-     kernels) + csrc/fa_paged_window_inst.hip x 16 and csrc/fa_paged_fp8_window_inst.hip x 16 (their
-     sliding-window variants) + csrc/fa_paged_prefill_inst.hip x 16 (the paged fa_fwd_w4) + csrc/fa_fwd_gfx950.hip,
-     csrc/fa_paged_gfx950.hip, csrc/fa_paged_fp8_gfx950.hip, csrc/fa_paged_window_gfx950.hip,
-     csrc/fa_paged_prefill_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip (stand-alone kernels with
-     their entries)
+     head-dim tile x exact-D instantiation, compiled in parallel) + the other INST_TUS x 16 (the paged
+     decode kernels, the FP8 paged decode kernels, their sliding-window variants and the paged fa_fwd_w4, the
+     same combinations) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip, csrc/fa_paged_prefill_gfx950.hip
+     (C-ABI dispatchers) + csrc/fa_rope.hip, csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip (stand-alone kernels
+     with their entries)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
      include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h and
      include/fa_gfx950_paged_prefill.h; no torch symbols)
@@ -75,6 +73,13 @@ def abi_sources() -> list[Path]:
 # (dtype, causal, head-dim tile, exact head dim): must match FA_FOR_EACH_INSTANCE in csrc/fa_launch.h
 INSTANCES = [(dt, c, d, e) for dt in ("F16", "BF16") for c in (0, 1) for d in (64, 128) for e in (0, 1)]
 
+# The instantiation translation units: (directory prefix, csrc/<name>.hip), each compiled once per INSTANCES
+# entry into build/obj/<prefix><dtype>_c<causal>_d<tile>_x<exact>/ -- the dense kernels, the paged decode, its
+# FP8 pool, their sliding-window variants, and the paged fa_fwd_w4 (the paged prefill)
+INST_TUS = (("", "fa_inst"), ("paged_", "fa_paged_inst"), ("fp8_", "fa_paged_fp8_inst"),
+            ("win_", "fa_paged_window_inst"), ("win8_", "fa_paged_fp8_window_inst"),
+            ("pfill_", "fa_paged_prefill_inst"))
+
 HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
              "-ffinite-math-only", "-fno-signed-zeros"]
 
@@ -136,58 +141,13 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     objs = []
     asm_files = []
     tooling = [Path(__file__).resolve()]
-    headers = [CSRC / "fa_launch.h", *sorted(INCLUDE.glob("*.h"))]
-    inst_deps = [p for ext in ("*.hpp", "*.h", "*.inc") for p in sorted(CSRC.glob(ext))] + [CSRC / "fa_inst.hip"]
-    for dt, c, d, e in INSTANCES:
-        # one directory per instantiation: -save-temps=obj names its files after the source
-        idir = objdir / f"{dt.lower()}_c{c}_d{d}_x{e}"
-        idir.mkdir(parents=True, exist_ok=True)
-        obj = idir / "fa_inst.o"
-        objs.append(obj)
-        stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
-        if not stub:
-            asm_files.append(idir / f"fa_inst-hip-amdgcn-amd-amdhsa-{ARCH}.s")
-        cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
-                      f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
-                      "-Wno-inline-asm", "-c", CSRC / "fa_inst.hip", "-o", obj], obj, inst_deps + tooling))
-    # the paged decode kernels (csrc/fa_paged_inst.hip), one translation unit per combination as well, in
-    # directories of their own: the dense instantiations above compile exactly as without them
-    paged_deps = inst_deps + [CSRC / "fa_paged_inst.hip"]
-    for dt, c, d, e in INSTANCES:
-        idir = objdir / f"paged_{dt.lower()}_c{c}_d{d}_x{e}"
-        idir.mkdir(parents=True, exist_ok=True)
-        obj = idir / "fa_paged_inst.o"
-        objs.append(obj)
-        stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
-        if not stub:
-            asm_files.append(idir / f"fa_paged_inst-hip-amdgcn-amd-amdhsa-{ARCH}.s")
-        cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
-                      f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
-                      "-Wno-inline-asm", "-c", CSRC / "fa_paged_inst.hip", "-o", obj], obj, paged_deps + tooling))
-    # the FP8 paged decode kernels (csrc/fa_paged_fp8_inst.hip), the same combinations again, in directories
-    # whose names match neither pattern above; their objects also depend on the public headers
-    fp8_deps = inst_deps + [CSRC / "fa_paged_fp8_inst.hip", *sorted(INCLUDE.glob("*.h"))]
-    for dt, c, d, e in INSTANCES:
-        idir = objdir / f"fp8_{dt.lower()}_c{c}_d{d}_x{e}"
-        idir.mkdir(parents=True, exist_ok=True)
-        obj = idir / "fa_paged_fp8_inst.o"
-        objs.append(obj)
-        stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
-        if not stub:
-            asm_files.append(idir / f"fa_paged_fp8_inst-hip-amdgcn-amd-amdhsa-{ARCH}.s")
-        cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
-                      f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
-                      "-Wno-inline-asm", "-c", CSRC / "fa_paged_fp8_inst.hip", "-o", obj], obj, fp8_deps + tooling))
-    # the sliding-window variants of the paged and FP8 paged decode kernels (csrc/fa_paged_window_inst.hip,
-    # csrc/fa_paged_fp8_window_inst.hip), the same combinations, in directories that none of the patterns above
-    # match: the unwindowed instantiations compile exactly as without them
-    # and the paged variant of fa_fwd_w4 (csrc/fa_paged_prefill_inst.hip, the paged prefill), the same way: the
-    # dense fa_inst objects compile exactly as without it, and its assembly takes the whole fa_fwd_w4 gate
-    for prefix, name in (("win", "fa_paged_window_inst"), ("win8", "fa_paged_fp8_window_inst"),
-                         ("pfill", "fa_paged_prefill_inst")):
-        win_deps = fp8_deps + [CSRC / f"{name}.hip"]
+    headers = [*sorted(CSRC.glob("*.h")), *sorted(INCLUDE.glob("*.h"))]
+    inst_deps = ([p for ext in ("*.hpp", "*.h", "*.inc") for p in sorted(CSRC.glob(ext))]
+                 + sorted(INCLUDE.glob("*.h")))
+    for prefix, name in INST_TUS:
         for dt, c, d, e in INSTANCES:
-            idir = objdir / f"{prefix}_{dt.lower()}_c{c}_d{d}_x{e}"
+            # one directory per instantiation: -save-temps=obj names its files after the source
+            idir = objdir / f"{prefix}{dt.lower()}_c{c}_d{d}_x{e}"
             idir.mkdir(parents=True, exist_ok=True)
             obj = idir / f"{name}.o"
             objs.append(obj)
@@ -196,11 +156,11 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
                 asm_files.append(idir / f"{name}-hip-amdgcn-amd-amdhsa-{ARCH}.s")
             cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
                           f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
-                          "-Wno-inline-asm", "-c", CSRC / f"{name}.hip", "-o", obj], obj, win_deps + tooling))
-    # C-ABI dispatchers (dense, paged, FP8 paged, sliding-window paged), standalone RoPE kernel, KV-cache append
-    # kernels
-    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_fp8_gfx950.hip", "fa_paged_window_gfx950.hip",
-                "fa_paged_prefill_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip"):
+                          "-Wno-inline-asm", "-c", CSRC / f"{name}.hip", "-o", obj], obj,
+                         inst_deps + [CSRC / f"{name}.hip"] + tooling))
+    # C-ABI dispatchers (dense, paged decode, paged prefill), standalone RoPE kernel, KV-cache append kernels
+    for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_rope.hip",
+                "fa_kvcache.hip", "fa_kvcache_fp8.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src, "-o", obj], obj,
@@ -210,8 +170,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         stamp = obj.with_suffix(".cmd")
         line = " ".join(map(str, cmd))
         if (not force and not _stale(obj, deps) and stamp.exists() and stamp.read_text() == line
-                and (obj.name not in ("fa_inst.o", "fa_paged_inst.o", "fa_paged_fp8_inst.o", "fa_paged_window_inst.o",
-                                     "fa_paged_fp8_window_inst.o", "fa_paged_prefill_inst.o")
+                and (obj.name not in [f"{name}.o" for _, name in INST_TUS]
                      or next(obj.parent.glob("*.s"), None) is not None)):
             return
         _run(cmd, verbose)

@@ -5,11 +5,11 @@
 // The two descales cost nothing in the key loop: k_descale folds into the softmax scale, v_descale into
 // the final 1 / l.
 //
-// Carried over from fa_decode_body.inc / PagedKv unchanged in structure: the work decode, the scalar page
-// id fetched one tile ahead, the per-wave LDS ring filled by LDS-DMA and retired by counted vmcnt waits
-// (no barrier in the key loop), the online softmax with the deferred rescale, the four-wave LDS merge and
-// the fp32 partials with the fused (decode_merge) / unfused (fa_decode_combine) combine, which are shared
-// functions. What differs is the K / V image and its fragments:
+// The kernel is decode_body (fa_decode.hpp) with the PagedKv8 policy below: the work decode, the scalar page
+// id fetched one tile ahead (PagedWalk<1>), the per-wave LDS ring filled by LDS-DMA and retired by counted
+// vmcnt waits (no barrier in the key loop), the online softmax with the deferred rescale, the four-wave LDS
+// merge and the fp32 partials with the fused (decode_merge) / unfused (fa_decode_combine) combine are the
+// 16-bit kernels' own code. What the policy changes is the K / V image and its fragments:
 //
 //   * a row is kD BYTES (128 / 64), a 32-key tile 4 / 2 KiB, a 16-byte LDS-DMA chunk 16 elements;
 //   * K (A operand of S^T = K.Q^T): lane (h, r) reads ONE ds_read_b128 per pair of k-steps (2j, 2j + 1):
@@ -34,8 +34,7 @@
 // 16-bit kernel's bytes in flight per wave in the same 128 KiB of LDS. Measured (same process, -DFA_FP8_RING=4
 // against 2, profiles/fp8_decode_ab.json), the two-slot ring is 5-6 % FASTER on both shapes, so the ring
 // stays two slots deep (64 KiB of LDS); DESIGN.md "FP8 KV cache" has the A/B.
-#include "fa_decode.hpp"
-#include "fa_paged_fp8_launch.h"
+#include "fa_decode_paged.hpp"
 
 #ifndef FA_FP8_RING
 #define FA_FP8_RING 2
@@ -97,80 +96,96 @@ __device__ __forceinline__ void wait_tiles(const int n) {
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * kPer) : "memory");
 }
 
-// PagedKv over 1-byte elements: the same walk (one call per tile in increasing t, the next page's id
-// fetched by a scalar load one tile ahead, the id clamped into the pool, a 64-bit page term).
-struct PagedKv8 {
-    typedef const __attribute__((address_space(4))) int32_t *table_t;  // (constant space: a scalar load)
-    const char *kh, *vh;  // the pool at this kv-head
-    int64_t kps, vps;     // page strides, bytes
-    int ks_, vs_;
-    table_t row;
-    int tpp, last_page, t_hi;
-    int pi, tip, phys;
+// The paged FP8 pool (ArgsT: PagedFp8DecArgs, or PagedFp8WinDecArgs for the windowed kernel)
+template <int kD, class ArgsT = PagedFp8DecArgs>
+struct PagedKv8 : Fp8Geo<kD>, PagedSeq<1, ArgsT> {
+    using PagedSeq<1, ArgsT>::PagedSeq;
+    using FG = Fp8Geo<kD>;
+    using FG::RB;
+    using FG::kPieces;
+    static constexpr int kElem = 1;         // bytes of a K / V element
+    static constexpr int kRing = kFp8Ring;  // slots of a wave's LDS ring
+    static constexpr int KS = Geo<kD>::kKSteps, KP = FG::kPairs, DTL = Geo<kD>::kDTiles;
+    typedef const __attribute__((address_space(4))) float *scale_t;  // (constant space: scalar loads)
 
-    __device__ __forceinline__ PagedKv8(const fa_fwd_params &p, const PagedDecArgs &a, int b, int hkv, int t_lo,
-                                        int t_hi_)
-        : kps(p.k_batch_stride), vps(p.v_batch_stride), ks_((int)p.k_seqlen_stride), vs_((int)p.v_seqlen_stride),
-          tpp(a.tiles_per_page), last_page(a.num_pages - 1), t_hi(t_hi_) {
-        kh = (const char *)p.k_ptr + (int64_t)hkv * p.k_head_stride;
-        vh = (const char *)p.v_ptr + (int64_t)hkv * p.v_head_stride;
-        row = (table_t)(a.block_table + (int64_t)b * a.block_table_stride);
-        pi = t_lo / tpp;
-        tip = t_lo - pi * tpp;
-        phys = t_lo < t_hi ? row[pi] : 0;  // (a wave without tiles reads no entry)
+    // the descales of this (batch row, kv-head): k folds into the softmax scale, v into the final 1 / l
+    static __device__ __forceinline__ void scale(const fa_fwd_params &p, const ArgsT &a, const int b, const int hkv,
+                                                 float &sc, float &vds) {
+        const int64_t dso = (int64_t)b * a.descale_batch_stride + (int64_t)hkv * a.descale_head_stride;
+        const float kds = a.k_descale ? ((scale_t)a.k_descale)[dso] : 1.f;
+        vds = a.v_descale ? ((scale_t)a.v_descale)[dso] : 1.f;
+        sc = p.softmax_scale * kds;
     }
-    __device__ __forceinline__ void tile(int t, const char *&k, const char *&v) {
-        const int64_t page = min(max(phys, 0), last_page);
-        const int64_t r0 = (int64_t)(tip * kDecKeys);
-        k = kh + page * kps + r0 * ks_;
-        v = vh + page * vps + r0 * vs_;
-        if (++tip == tpp) {
-            tip = 0;
-            ++pi;
-            if (t + 1 < t_hi) phys = row[pi];  // the next tile's page, one tile ahead of its use
+    // bytes of the first `rows` rows of a [rows, D] slab of 1-byte elements with row stride `stride`
+    static __device__ __forceinline__ uint32_t slab(int rows, int stride, int D) {
+        return rows <= 0 ? 0u : (uint32_t)((rows - 1) * stride + D);
+    }
+    // B operand of S^T = K.Q^T in K's d order: lane (h, r) holds Q[row r][32 j + 16 h + 8 e .. + 7] for
+    // k-step 2 j + e
+    static __device__ __forceinline__ int q_chunk(int ks, int h) { return 4 * (ks >> 1) + 2 * h + (ks & 1); }
+
+    // after the ring's first n_pre tiles (decode_body issues them): the counted wait retires the Q pieces
+    // (issued first) and leaves the tiles in flight
+    static constexpr bool kStraightPrefill = false;
+    static __device__ __forceinline__ void wait_prefill(const int n_pre) { wait_tiles<2 * kPieces>(n_pre); }
+    // tile t landed (the younger tiles of the ring may still be in flight)
+    static __device__ __forceinline__ void wait_tile(const int t, const int t_hi) {
+        wait_tiles<2 * kPieces>(min(t_hi - 1 - t, kRing - 1));
+    }
+
+    struct Frags {
+        int v_addr[DTL], k_addr[KP];
+        u32x4 k8[KP];
+        u32x2 v8[2][DTL];
+
+        __device__ __forceinline__ Frags(const int lane) {
+            const int r = lane & 31, h = lane >> 5;
+            const int g4 = lane >> 4, q = (lane >> 1) & 7, pp = lane & 1;
+            const int row0 = 4 * (g4 >> 1) + (q & 3) + 8 * (q >> 2);
+#pragma unroll
+            for (int dt = 0; dt < DTL; ++dt) v_addr[dt] = FG::v_off(row0, 2 * dt + (g4 & 1)) + 8 * pp;
+#pragma unroll
+            for (int j = 0; j < KP; ++j) k_addr[j] = FG::k_off(r, 2 * j + h);
         }
-    }
+        __device__ __forceinline__ void load(const char *K, const char *V) {
+#pragma unroll
+            for (int j = 0; j < KP; ++j) k8[j] = *(const u32x4 *)(K + k_addr[j]);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int dt = 0; dt < DTL; ++dt) v8[kk][dt] = tr8_read(V + kk * 16 * RB + v_addr[dt]);
+        }
+        template <class DT>
+        __device__ __forceinline__ f32x16 qk(const u32x4 (&qf)[KS]) const {
+            f32x16 s = {};
+#pragma unroll
+            for (int j = 0; j < KP; ++j) {
+                s = DT::mfma(widen8<DT>(k8[j][0], k8[j][1]), qf[2 * j], s);
+                s = DT::mfma(widen8<DT>(k8[j][2], k8[j][3]), qf[2 * j + 1], s);
+            }
+            return s;
+        }
+        template <class DT>
+        __device__ __forceinline__ void pv(const u32x4 (&pf)[2], f32x16 (&o)[DTL]) const {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int dt = 0; dt < DTL; ++dt)
+                    o[dt] = DT::mfma(widen8<DT>(v8[kk][dt][0], v8[kk][dt][1]), pf[kk], o[dt]);
+        }
+    };
 };
 
-// bytes of the first `rows` rows of a [rows, D] slab of 1-byte elements with row stride `stride`
-__device__ __forceinline__ uint32_t slab_bytes8(int rows, int stride, int D) {
-    return rows <= 0 ? 0u : (uint32_t)((rows - 1) * stride + D);
-}
-
-// (the body is a textual include, as fa_decode_body.inc: fa_decode_paged_fp8_window.hpp expands it once more
-// with FA_DEC_WINDOW 1, and this kernel keeps its tokens)
 template <class DT, bool kCausal, int kD, bool kExactD, bool kFuse = false>
 __global__ __launch_bounds__(256, 1) void fa_decode_fp8kv(const fa_fwd_params p, const PagedFp8DecArgs a) {
-#include "fa_decode_fp8_body.inc"
+    decode_body<PagedKv8<kD>, false, DT, kCausal, kD, kExactD, kFuse>(p, a);
 }
 
-// as launch_decode_paged: the FP8 kernel (+ the split combine when a.n_split > 1 and the merge is not fused)
 template <class DT, bool C, int kD, bool kExact>
 int launch_decode_paged_fp8(const fa_fwd_params &p, PagedFp8DecArgs a, void *ws, hipStream_t stream) {
-    const int64_t units = decode_units(p, a);
-    if (a.n_split > 1) {
-        const int64_t slots = units * a.n_split * kDecRows;
-        a.ws_o = (float *)ws;
-        a.ws_lse = (float *)((char *)ws + slots * kD * 4);
-    }
-    if (a.n_split > 1 && knobs().dec_fuse && same_xcd_placement()) {
-        unsigned *err = nullptr;
-        a.cnt = split_sync_area(stream, units * 4, &err);
-    }
-    set_last_dec_fused(a.cnt != nullptr);
-    const int64_t grid = a.cnt ? 8 * ((units + 7) / 8) * a.n_split : units * a.n_split;
-    if (a.cnt)
-        hipLaunchKernelGGL((fa_decode_fp8kv<DT, C, kD, kExact, true>), dim3((uint32_t)grid), dim3(256), 0, stream, p, a);
-    else
-        hipLaunchKernelGGL((fa_decode_fp8kv<DT, C, kD, kExact>), dim3((uint32_t)grid), dim3(256), 0, stream, p, a);
-    if (a.n_split > 1 && !a.cnt)
-        hipLaunchKernelGGL((fa_decode_combine<DT, kD, kExact>),
-                           dim3((uint32_t)(p.batch_size * p.num_heads_kv * ((a.rows + 3) / 4))), dim3(256), 0, stream,
-                           p, static_cast<const DecArgs &>(a));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-    set_last_path(a.n_split > 1 ? kPathDecodePagedFp8Split : kPathDecodePagedFp8);
-    return FA_OK;
+    return launch_decode_kernels<DT, kD, kExact>(p, a, ws, stream, &fa_decode_fp8kv<DT, C, kD, kExact, true>,
+                                                 &fa_decode_fp8kv<DT, C, kD, kExact, false>, kPathDecodePagedFp8,
+                                                 kPathDecodePagedFp8Split);
 }
 
 }  // namespace fa

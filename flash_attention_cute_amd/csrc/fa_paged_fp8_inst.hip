@@ -6,7 +6,7 @@
 #ifndef FA_INST_STUB
 #include "fa_decode_paged_fp8.hpp"
 #else
-#include "fa_paged_fp8_launch.h"
+#include "fa_paged_launch.h"
 namespace fa {
 template <class DT, bool C, int kD, bool kExact>
 int launch_decode_paged_fp8(const fa_fwd_params &, PagedFp8DecArgs, void *, hipStream_t) {

@@ -1,6 +1,6 @@
 // fa_paged_prefill_gfx950.hip -- C-ABI of the paged prefill (include/fa_gfx950_paged_prefill.h).
 //
-// Host code only, beside fa_paged_gfx950.hip and fa_paged_window_gfx950.hip, which it does not change:
+// Host code only, beside fa_paged_gfx950.hip (the paged decode entries), which it does not change:
 // validation is fa_fwd_gfx950_paged_check's and fa_fwd_gfx950_check's through their public entries, so this
 // entry and the decode entries cannot drift apart, plus the one rule that is new here (a page holds whole
 // 64-key tiles); the dtype / causal / head-dim dispatch goes to the paged fa_fwd_w4 instantiations

@@ -6,7 +6,7 @@
 #ifndef FA_INST_STUB
 #include "fa_decode_paged_window.hpp"
 #else
-#include "fa_paged_window_launch.h"
+#include "fa_paged_launch.h"
 namespace fa {
 template <class DT, bool C, int kD, bool kExact>
 int launch_decode_paged_window(const fa_fwd_params &, PagedWinDecArgs, void *, hipStream_t) {

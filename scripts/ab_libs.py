@@ -109,4 +109,6 @@ for rep in range(int(os.environ.get("AB_REPS", "5"))):
 for i, p in enumerate(sys.argv[2:]):
     r = sorted(res[i])
     d = (outs[i].float() - outs[0].float()).abs().max().item()
-    print(f"{sys.argv[1]} {p}: median {r[len(r) // 2]:.1f} TFLOPS  (min {r[0]:.1f} max {r[-1]:.1f})  max|o-o0| {d:.2e}")
+    eq = torch.equal(outs[i], outs[0])  # (bit for bit the first library's output)
+    print(f"{sys.argv[1]} {p}: median {r[len(r) // 2]:.1f} TFLOPS  (min {r[0]:.1f} max {r[-1]:.1f})  max|o-o0| {d:.2e}"
+          f"  equal {eq}")

@@ -1,7 +1,8 @@
 """Same-process A/B of the sliding-window paged decode, and of the unwindowed paged decodes against another
 build of the library.
 
-    timeout -k 10 900 python scripts/bench_window_decode.py [--rounds R] [--inner N] [--parent-lib LIB.so] [--out FILE.json]
+    timeout -k 10 900 python scripts/bench_window_decode.py [--rounds R] [--inner N] [--parent-lib LIB.so]
+                                                            [--regression-only] [--out FILE.json]
 
 Window arms (``flash_attn_paged_func``; bf16 q, Hq 32 / Hkv 8 / D 128, page size 64, shuffled pages, window_left
 4095), on a 16-bit pool and on an FP8 (e4m3) pool, for B 16 with lengths spread over 8192..32768 and for B 1 with
@@ -20,9 +21,11 @@ agree within the 16-bit tolerance (not bit for bit: the window may start mid-til
 Regression arms (``--parent-lib``: the library of another build, e.g. the parent commit's): the UNWINDOWED 16-bit
 and FP8 paged decodes (fa_fwd_gfx950_paged, fa_fwd_gfx950_paged_fp8) of this build's library and of that one,
 called through the C ABI on the same buffers, on bench_paged_decode.py's shapes (B 32 capacity 4096 lengths
-1024..4000; B 1 131072 keys) at page size 64. Every round times new, parent, new again; recorded: the ratio
-new / parent (new = the mean of its two medians) and the spread |new - new'| / mean. The outputs of the two
-libraries are checked bit-equal before timing.
+1024..4000; B 1 131072 keys) at page size 64, and the WINDOWED ones (fa_fwd_gfx950_paged_window,
+fa_fwd_gfx950_paged_window_fp8, window_left 4095) on the window shapes above. Every round times new, parent, new
+again; recorded: the ratio new / parent (new = the mean of its two medians), the spread |new - new'| / mean and
+whether new / parent <= 1 + 2 x that spread. The outputs of the two libraries are checked bit-equal before timing.
+``--regression-only`` skips the window arms.
 
 Prints one JSON object (and writes it to ``--out``, by default profiles/window_decode_ab.json).
 """
@@ -148,9 +151,10 @@ class PagedFp8Params(ctypes.Structure):  # include/fa_gfx950_fp8.h fa_paged_fp8_
                 ("descale_batch_stride", ctypes.c_int64), ("descale_head_stride", ctypes.c_int64)]
 
 
-def abi_call(lib, fp8, q, o, kc, vc, table, sl, kd, vd):
-    """A closure that launches the unwindowed paged decode of `lib` on the current stream: the Sq == 1 decode
-    step as the binding passes it (the q-heads of a kv group packed into the rows of an MHA problem)."""
+def abi_call(lib, fp8, q, o, kc, vc, table, sl, kd, vd, window_left=None):
+    """A closure that launches the paged decode of `lib` (window_left None: the unwindowed entry) on the current
+    stream: the Sq == 1 decode step as the binding passes it (the q-heads of a kv group packed into the rows of
+    an MHA problem)."""
     g = HQ // HKV
     base = FwdParams(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), o.data_ptr(), q.size(0), HKV, HKV, g,
                      table.size(1) * PAGE, D, 1,
@@ -158,19 +162,21 @@ def abi_call(lib, fp8, q, o, kc, vc, table, sl, kd, vd):
                      D, kc.stride(2), vc.stride(2), D, D ** -0.5 * 1.4426950408889634)
     paged = PagedParams(base, table.data_ptr(), table.stride(0), table.size(1), kc.size(0), PAGE, sl.data_ptr())
     p = PagedFp8Params(paged, kd.data_ptr(), vd.data_ptr(), HKV, 1) if fp8 else paged
-    stem = "fa_fwd_gfx950_paged_fp8" if fp8 else "fa_fwd_gfx950_paged"
+    win = () if window_left is None else (ctypes.c_int64(window_left),)
+    stem = "fa_fwd_gfx950_paged" + ("_window" if win else "") + ("_fp8" if fp8 else "")
     size = getattr(lib, stem + "_workspace_size")
     size.restype = ctypes.c_int64
-    n = size(ctypes.byref(p), 1, 0)
+    n = size(ctypes.byref(p), 1, 0, *win)
     if n < 0:
         raise AssertionError(f"{stem}_workspace_size failed")
     ws = torch.empty(max(n, 16), dtype=torch.uint8, device=q.device)
     fn = getattr(lib, stem)
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    fn.argtypes = ([ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * len(win)
+                   + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
     stream = torch.cuda.current_stream().cuda_stream
 
     def call():
-        rc = fn(ctypes.byref(p), 1, 0, ws.data_ptr() if n > 0 else None, n, stream)
+        rc = fn(ctypes.byref(p), 1, 0, *win, ws.data_ptr() if n > 0 else None, n, stream)
         if rc != 0:
             raise AssertionError(f"{stem} failed ({rc})")
 
@@ -178,28 +184,29 @@ def abi_call(lib, fp8, q, o, kc, vc, table, sl, kd, vd):
     return call
 
 
-def run_regression_shape(name, s, fp8, new_lib, parent_lib, rounds, inner, dev):
+def run_regression_shape(name, s, fp8, new_lib, parent_lib, rounds, inner, dev, window_left=None):
     gen = torch.Generator(device=dev).manual_seed(2)
     q = torch.randn(s["B"], HQ, 1, D, generator=gen, device=dev, dtype=BF16)
     kc, vc, table = random_pool(s["B"], s["cap"], fp8, gen, dev)
     sl = torch.tensor(s["lens"], dtype=torch.int32, device=dev)
     kd, vd = torch.full((s["B"], HKV), 0.5, device=dev), torch.full((s["B"], HKV), 2.0, device=dev)
     o_new, o_parent = torch.empty_like(q), torch.empty_like(q)
-    new = abi_call(new_lib, fp8, q, o_new, kc, vc, table, sl, kd, vd)
-    parent = abi_call(parent_lib, fp8, q, o_parent, kc, vc, table, sl, kd, vd)
+    new = abi_call(new_lib, fp8, q, o_new, kc, vc, table, sl, kd, vd, window_left)
+    parent = abi_call(parent_lib, fp8, q, o_parent, kc, vc, table, sl, kd, vd, window_left)
     new()
     parent()
     torch.cuda.synchronize()
     if not torch.equal(o_new, o_parent):
-        raise AssertionError(f"{name}: the unwindowed decode of the two libraries differs")
+        raise AssertionError(f"{name}: the decode of the two libraries differs")
     med = timed([("new", new), ("parent", parent), ("new2", new)], rounds, inner)
     new_ms = 0.5 * (med["new"] + med["new2"])
     spread = 100.0 * abs(med["new"] - med["new2"]) / new_ms
     ratio = new_ms / med["parent"]
     return {"shape": name, "cache": "fp8" if fp8 else "bf16", "B": s["B"], "capacity": s["cap"], "page_size": PAGE,
-            "bit_equal": True, "new_ms": round(med["new"], 5), "parent_ms": round(med["parent"], 5),
+            "window_left": window_left, "bit_equal": True, "new_ms": round(med["new"], 5), "parent_ms": round(med["parent"], 5),
             "new2_ms": round(med["new2"], 5), "ratio_new_over_parent": round(ratio, 4),
-            "aa_spread_pct": round(spread, 3), "within_twice_the_spread": abs(ratio - 1.0) * 100.0 <= 2.0 * spread}
+            "aa_spread_pct": round(spread, 3), "within_twice_the_spread": abs(ratio - 1.0) * 100.0 <= 2.0 * spread,
+            "not_slower_than_twice_the_spread": (ratio - 1.0) * 100.0 <= 2.0 * spread}
 
 
 def main():
@@ -207,6 +214,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=31)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--parent-lib", default=None, help="libfa_gfx950.so of the build to compare the unwindowed decodes with")
+    ap.add_argument("--regression-only", action="store_true", help="skip the window arms (a / b / c)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "window_decode_ab.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -217,7 +225,8 @@ def main():
               "method": "median over rounds of (inner calls between two device events) / inner; window arms per round: "
                         "a (windowed, full cache), b (unwindowed, full cache), c (unwindowed, the window's keys only), c "
                         "again; regression arms per round: new, parent, new again",
-              "window": [run_window_shape(n, s, fp8, args.rounds, args.inner, dev)
+              "window": [] if args.regression_only else
+                        [run_window_shape(n, s, fp8, args.rounds, args.inner, dev)
                          for fp8 in (False, True) for n, s in WINDOW_SHAPES.items()]}
     if args.parent_lib:
         from flash_attention_cute_amd import _build
@@ -225,6 +234,8 @@ def main():
         new_lib, parent_lib = ctypes.CDLL(str(_build.ABI_LIB)), ctypes.CDLL(str(Path(args.parent_lib).resolve()))
         result["regression"] = [run_regression_shape(n, s, fp8, new_lib, parent_lib, args.rounds, args.inner, dev)
                                 for fp8 in (False, True) for n, s in REGRESSION_SHAPES.items()]
+        result["regression"] += [run_regression_shape(n, s, fp8, new_lib, parent_lib, args.rounds, args.inner, dev, W)
+                                 for fp8 in (False, True) for n, s in WINDOW_SHAPES.items()]
     text = json.dumps(result, indent=1)
     print(text, flush=True)
     if args.out:

@@ -852,8 +852,8 @@ def test_out_of_range_lengths_are_clamped_to_the_table(dbg, kernel):
     """Lengths (-3, cap + 1, cap + page + 5, 2^31 - 1, -2^31) give the bits of (0, cap, cap, cap, 0). The table is
     the first max_pages columns of a WIDER int32 tensor (a row stride != max_pages) whose further columns name
     NaN-poisoned pages: a length that escaped the clamp would walk into them and show as NaN, not as an access
-    outside the table. (The clamps: fa_decode_body.inc, fa_decode_fp8_body.inc, fa_fwd_kernels.hpp set_block --
-    each precedes every use of the length.)"""
+    outside the table. (The clamps: fa_decode_paged.hpp PagedSeq::key_range, fa_fwd_kernels.hpp set_block -- each
+    precedes every use of the length.)"""
     from flash_attention_cute_amd import flash_attn_paged_func
 
     sq, w, fp8, want_path = CLAMP[kernel]

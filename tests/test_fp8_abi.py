@@ -248,7 +248,7 @@ def test_debug_names_of_the_fp8_paths():
     from flash_attention_cute_amd import _debug
 
     assert _debug.PATHS[11] == "decode_paged_fp8" and _debug.PATHS[12] == "decode_paged_fp8_split"
-    text = (ROOT / "flash_attention_cute_amd" / "csrc" / "fa_paged_fp8_launch.h").read_text()
+    text = (ROOT / "flash_attention_cute_amd" / "csrc" / "fa_paged_launch.h").read_text()
     assert "kPathDecodePagedFp8 = 11" in text and "kPathDecodePagedFp8Split = 12" in text
 
 
@@ -285,7 +285,7 @@ def test_fp8_asm_gate_passes_on_the_built_instantiations():
 
 
 def test_fp8_host_validation_under_asan_ubsan(tmp_path):
-    """The FP8 dispatcher's and the quantizing append's host code (csrc/fa_paged_fp8_gfx950.hip,
+    """The FP8 entries' and the quantizing append's host code (csrc/fa_paged_gfx950.hip,
     csrc/fa_kvcache_fp8.hip, with the 16-bit dispatchers they validate through) built with AddressSanitizer
     + UBSan on the host side only and linked with host-only stub instantiations, run as a stand-alone
     program (tests/asan/fp8_validation_driver.cpp)."""
@@ -299,9 +299,9 @@ def test_fp8_host_validation_under_asan_ubsan(tmp_path):
            "-Xarch_host", "-fno-sanitize-recover=undefined"]
     base = [hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", *san, *inc, "-c"]
     objs = []
-    for src in (csrc / "fa_fwd_gfx950.hip", csrc / "fa_paged_gfx950.hip", csrc / "fa_paged_fp8_gfx950.hip",
-                csrc / "fa_kvcache.hip", csrc / "fa_kvcache_fp8.hip", asan / "stub_instances.hip",
-                asan / "paged_stub_instances.hip", asan / "fp8_stub_instances.hip", asan / "fp8_validation_driver.cpp"):
+    for src in (csrc / "fa_fwd_gfx950.hip", csrc / "fa_paged_gfx950.hip", csrc / "fa_kvcache.hip",
+                csrc / "fa_kvcache_fp8.hip", asan / "stub_instances.hip", asan / "paged_stub_instances.hip",
+                asan / "fp8_validation_driver.cpp"):
         obj = tmp_path / (src.stem + ".o")
         subprocess.run([*base, str(src), "-o", str(obj)], check=True, capture_output=True)
         objs.append(str(obj))

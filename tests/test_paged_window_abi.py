@@ -197,9 +197,9 @@ def test_window_asm_gate_passes_on_the_built_instantiations():
 
 
 def test_window_host_validation_under_asan_ubsan(tmp_path):
-    """The window dispatcher's host code (csrc/fa_paged_window_gfx950.hip, with the three dispatchers it validates
-    and plans through) built with AddressSanitizer + UBSan on the host side only and linked with the existing
-    host-only stub instantiations plus those of the windowed launches, run as a stand-alone program
+    """The window entries' host code (csrc/fa_paged_gfx950.hip, with the dense dispatcher it validates through)
+    built with AddressSanitizer + UBSan on the host side only and linked with the host-only stub
+    instantiations, those of the windowed launches among them, run as a stand-alone program
     (tests/asan/paged_window_validation_driver.cpp)."""
     hipcc = "/opt/rocm/bin/hipcc"
     if not shutil.which(hipcc):
@@ -211,10 +211,8 @@ def test_window_host_validation_under_asan_ubsan(tmp_path):
            "-Xarch_host", "-fno-sanitize-recover=undefined"]
     base = [hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", *san, *inc, "-c"]
     objs = []
-    for src in (csrc / "fa_fwd_gfx950.hip", csrc / "fa_paged_gfx950.hip", csrc / "fa_paged_fp8_gfx950.hip",
-                csrc / "fa_paged_window_gfx950.hip", asan / "stub_instances.hip", asan / "paged_stub_instances.hip",
-                asan / "fp8_stub_instances.hip", asan / "paged_window_stub_instances.hip",
-                asan / "paged_window_validation_driver.cpp"):
+    for src in (csrc / "fa_fwd_gfx950.hip", csrc / "fa_paged_gfx950.hip", asan / "stub_instances.hip",
+                asan / "paged_stub_instances.hip", asan / "paged_window_validation_driver.cpp"):
         obj = tmp_path / (src.stem + ".o")
         subprocess.run([*base, str(src), "-o", str(obj)], check=True, capture_output=True)
         objs.append(str(obj))
