@@ -347,6 +347,13 @@ int check_params(const fa_fwd_params *p, int dtype, int causal) {
     const int64_t n_qtiles = (p->seqlen_q + fa::kBlockM - 1) / fa::kBlockM;
     const int64_t nwg = n_qtiles * p->num_heads_q * p->batch_size;
     if (nwg > 0x7fffffffLL) return set_err(FA_ERR_UNSUPPORTED, "grid too large (%lld workgroups)", (long long)nwg);
+    // the kernels track the running max of the UNSCALED scores and derive thr_raw = kRescaleThr / sc: sc > 0
+    // (on the bits: this file is built with -ffinite-math-only, under which a float test may drop NaN and inf)
+    uint32_t sc_bits;
+    __builtin_memcpy(&sc_bits, &p->softmax_scale, sizeof sc_bits);
+    if (sc_bits == 0 || sc_bits >= 0x7f800000u)  // +0, any negative value (sign bit), +inf, NaN
+        return set_err(FA_ERR_INVALID_ARGUMENT, "softmax_scale must be finite and > 0 (got %g)",
+                       (double)p->softmax_scale);
     g_err[0] = 0;
     return FA_OK;
 }

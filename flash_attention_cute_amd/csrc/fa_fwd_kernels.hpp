@@ -465,7 +465,9 @@ __global__ __launch_bounds__(kThreads) void fa_fwd_w8(const fa_fwd_params p, con
         if (__builtin_amdgcn_ballot_w64(grow)) {
             const float m_new = fmaxf(m_use, pair_max(mx));
             const float msc_new = (m_new <= kNeg) ? 0.f : m_new * sc;
-            alpha = __builtin_amdgcn_exp2f(msc - msc_new);  // msc == 0 && m_use == kNeg: l, O are 0
+            // a row's first visible key: O and l are still 0, alpha must not overflow (exp2(0 - msc_new) is +inf
+            // when the first tile's scores are below -128 log2 units, and 0 * inf is NaN)
+            alpha = (m_use <= 0.5f * kNeg) ? 0.f : __builtin_amdgcn_exp2f(msc - msc_new);
             m_use = m_new;
             msc = msc_new;
 #pragma unroll

@@ -22,6 +22,7 @@ same registrations (CPU default, "cuda" kernel, fake) and the same pad / contigu
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from typing import Optional
@@ -45,8 +46,14 @@ def _require_ext() -> None:
 
 
 def _default_scale(q: torch.Tensor, softmax_scale):
-    """``D ** -0.5`` on the UNPADDED head dim unless the caller gave a scale (reference :49-50)."""
-    return (q.size(-1) ** -0.5) if softmax_scale is None else softmax_scale
+    """``D ** -0.5`` on the UNPADDED head dim unless the caller gave a scale (reference :49-50). A given scale must
+    be finite and > 0 -- the kernels track the running max of the unscaled scores -- and is refused here as the
+    C-ABI refuses it (include/fa_gfx950.h), so the CPU defaults and the GPU kernels agree."""
+    if softmax_scale is None:
+        return q.size(-1) ** -0.5
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise RuntimeError(f"softmax_scale must be finite and > 0 (got {softmax_scale})")
+    return softmax_scale
 
 
 def _padded_call(fn, tensors, *args):

@@ -84,7 +84,7 @@ typedef struct fa_fwd_params {
     int64_t v_seqlen_stride;
     int64_t o_seqlen_stride;
 
-    float softmax_scale; /* scale * log2(e) */
+    float softmax_scale; /* scale * log2(e); finite and > 0, else FA_ERR_INVALID_ARGUMENT from every entry */
 } fa_fwd_params;
 
 /* dtype codes (reference csrc/kernel_dispatcher.h:20-34: kHalf, kBFloat16) */

@@ -106,6 +106,54 @@ def test_check_rejects(lib, kw, code, msg):
     assert rc == code and msg in err
 
 
+# softmax_scale must be finite and > 0 (include/fa_gfx950.h): the kernels track the running max of the UNSCALED scores
+BAD_SCALES = [0.0, -0.0, -0.1275, float("inf"), float("-inf"), float("nan"), -float("nan")]
+
+
+@pytest.mark.parametrize("scale", BAD_SCALES, ids=lambda s: repr(s))
+def test_every_dense_entry_rejects_a_scale_that_is_not_finite_and_positive(lib, scale):
+    """fa_fwd_gfx950_check and the varlen / padded checks, the sizing entries and every launch entry (validated
+    before the device is touched: NULL stream, bogus pointers) return FA_ERR_INVALID_ARGUMENT and name the field."""
+    lib.fa_last_error.restype = ctypes.c_char_p
+    for name in ("fa_fwd_gfx950_workspace_size", "fa_fwd_gfx950_padded_workspace_size"):
+        getattr(lib, name).restype = ctypes.c_int64
+    lib.fa_fwd_gfx950_window.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
+    lib.fa_fwd_gfx950_varlen_window.argtypes = lib.fa_fwd_gfx950_window.argtypes
+    lib.fa_fwd_gfx950_ws.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                     ctypes.c_void_p]
+    lib.fa_fwd_gfx950_padded.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.fa_fwd_gfx950_padded_workspace_size.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
+
+    class FaRopeFwdParams(ctypes.Structure):
+        _fields_ = [("base", FaFwdParams), ("rope_cos", ctypes.c_void_p), ("rope_sin", ctypes.c_void_p),
+                    ("rope_batch_stride", ctypes.c_int64), ("rope_seqlen_stride", ctypes.c_int64)]
+
+    for base in (good_params(softmax_scale=scale), decode_params()):
+        base.softmax_scale = scale
+        p, vp = ctypes.byref(base), ctypes.byref(FaVarlenParams(base, 0x50000, 0x60000))
+        pp = ctypes.byref(FaPaddedParams(base, None, None, 0x50000, 0x50100))
+        rp = ctypes.byref(FaRopeFwdParams(base, 0x70000, 0x80000, 0, 128))
+        calls = [lambda: lib.fa_fwd_gfx950_check(p, 0, 1), lambda: lib.fa_fwd_gfx950(p, 0, 1, None),
+                 lambda: lib.fa_fwd_gfx950_ws(p, 1, 0, None, 0, None),
+                 lambda: lib.fa_fwd_gfx950_window(p, 0, 1, 63, None),
+                 lambda: lib.fa_fwd_gfx950_rope(rp, 0, 1, None),
+                 lambda: lib.fa_fwd_gfx950_varlen_check(vp, 0, 1), lambda: lib.fa_fwd_gfx950_varlen(vp, 0, 1, None),
+                 lambda: lib.fa_fwd_gfx950_varlen_window(vp, 0, 1, 63, None),
+                 lambda: lib.fa_fwd_gfx950_padded(pp, 0, 1, -1, None, 0, None)]
+        for call in calls:
+            lib.fa_fwd_gfx950_check(ctypes.byref(good_params()), 0, 0)  # (clears the thread's message)
+            assert call() == FA_ERR_INVALID_ARGUMENT
+            assert b"softmax_scale" in lib.fa_last_error()
+        assert lib.fa_fwd_gfx950_workspace_size(p, 0, 1) == -1
+        assert lib.fa_fwd_gfx950_padded_workspace_size(pp, 0, 1, -1) == -1
+
+
+def test_the_smallest_positive_scales_are_accepted(lib):
+    for scale in (1e-3, 1.0, 1e-45, 3e38):  # (a subnormal and a near-maximal float: finite and > 0)
+        assert check(lib, good_params(softmax_scale=scale)) == (FA_OK, "")
+
+
 def test_check_rejects_dtype(lib):
     rc, err = check(lib, good_params(), dtype=7)
     assert rc == FA_ERR_UNSUPPORTED and "dtype" in err

@@ -157,6 +157,10 @@ def test_fp8_paged_check_accepts_valid(lib):
     ({"seqlen_kv": 4096 + 32}, FA_ERR_INVALID_ARGUMENT, "max_pages * page_size"),
     ({"descale_batch_stride": -1}, FA_ERR_INVALID_ARGUMENT, "descale strides"),
     ({"k_descale": 0x70002}, FA_ERR_INVALID_ARGUMENT, "4-byte aligned"),
+    ({"softmax_scale": 0.0}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": -0.1275}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": float("inf")}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": float("nan")}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
 ])
 def test_fp8_paged_check_and_launch_reject_without_touching_the_device(lib, kw, code, msg):
     p = fp8_params(**kw)

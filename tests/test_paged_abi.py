@@ -117,6 +117,10 @@ def test_paged_check_accepts_valid(lib):
     ({"k_seqlen_stride": 132}, FA_ERR_INVALID_ARGUMENT, "multiples of 8"),
     ({"v_batch_stride": 8 * 128 * 128 + 4}, FA_ERR_INVALID_ARGUMENT, "multiples of 8"),
     ({"headdim": 136}, FA_ERR_UNSUPPORTED, "<= 128"),
+    ({"softmax_scale": 0.0}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": -0.1275}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": float("inf")}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
+    ({"softmax_scale": float("nan")}, FA_ERR_INVALID_ARGUMENT, "softmax_scale"),
 ])
 def test_paged_check_and_launch_reject_without_touching_the_device(lib, kw, code, msg):
     p = paged_params(**kw)

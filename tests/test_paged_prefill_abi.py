@@ -91,9 +91,10 @@ def test_prefill_version_and_the_other_versions(lib):
 # decode-shaped parameter sets (page sizes that are multiples of 64): the verdict of the paged decode check
 ACCEPTED = [{}, {"page_size": 64, "max_pages": 64}, {"sq": 16, "pack": False},
             {"k_head_stride": 128, "v_head_stride": 128, "k_seqlen_stride": 8 * 128, "v_seqlen_stride": 8 * 128}]
+BAD_SCALES = [{"softmax_scale": s} for s in (0.0, -0.1275, float("inf"), float("nan"))]  # finite and > 0 only
 REJECTED = [{"page_size": 48}, {"page_size": 0}, {"block_table": None}, {"seqlens_k": 0x60002}, {"num_pages": 0},
             {"max_pages": 0}, {"seqlen_kv": 4096 + 64}, {"block_table_stride": 16}, {"k_seqlen_stride": 132},
-            {"headdim": 136}]
+            {"headdim": 136}] + BAD_SCALES
 
 
 def test_prefill_check_is_the_paged_check_for_decode_shapes(lib):
@@ -125,6 +126,17 @@ def test_prefill_check_takes_any_query_block_and_checks_the_pool_the_same_way(li
         want = lib.fa_fwd_gfx950_paged_check(ctypes.byref(paged_params(**kw)), 1, 1)
         assert lib.fa_fwd_gfx950_paged_prefill_check(ctypes.byref(chunk_params(**kw)), 1, 1) == want, kw
     assert lib.fa_fwd_gfx950_paged_prefill_check(ctypes.byref(chunk_params(q_seqlen_stride=132)), 1, 1) != FA_OK
+
+
+def test_prefill_entries_name_the_scale_they_reject(lib):
+    for kw in BAD_SCALES:
+        p = chunk_params(**kw)
+        assert lib.fa_fwd_gfx950_paged_prefill_check(ctypes.byref(chunk_params()), 1, 1) == FA_OK  # (clears the message)
+        assert lib.fa_fwd_gfx950_paged_prefill_check(ctypes.byref(p), 1, 1) == FA_ERR_INVALID_ARGUMENT
+        assert b"softmax_scale" in lib.fa_last_error()
+        for w in WINDOWS:
+            assert lib.fa_fwd_gfx950_paged_prefill(ctypes.byref(p), 1, 1, w, None, 0, None) == FA_ERR_INVALID_ARGUMENT
+            assert lib.fa_fwd_gfx950_paged_prefill_workspace_size(ctypes.byref(p), 1, 1, w) == -1
 
 
 @pytest.mark.parametrize("page_size", [32, 96])

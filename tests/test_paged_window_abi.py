@@ -91,9 +91,11 @@ def test_window_version_and_the_other_versions(lib):
 
 ACCEPTED = [{}, {"page_size": 32, "max_pages": 128}, {"sq": 16, "pack": False},
             {"k_head_stride": 128, "v_head_stride": 128, "k_seqlen_stride": 8 * 128, "v_seqlen_stride": 8 * 128}]
+BAD_SCALES = [{"softmax_scale": s} for s in (0.0, -0.1275, float("inf"), float("nan"))]  # finite and > 0 only
 REJECTED = [{"page_size": 48}, {"page_size": 0}, {"block_table": None}, {"seqlens_k": 0x60002}, {"num_pages": 0},
             {"max_pages": 0}, {"seqlen_kv": 4096 + 32}, {"block_table_stride": 16}, {"k_seqlen_stride": 132},
-            {"headdim": 136}, {"sq": 17, "pack": False}, {"hq": 40, "sq": 13, "pack": False}]
+            {"headdim": 136}, {"sq": 17, "pack": False}, {"hq": 40, "sq": 13, "pack": False}] + BAD_SCALES
+
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
@@ -115,6 +117,18 @@ def test_window_checks_are_the_unwindowed_checks_for_every_window(lib, kind):
     assert check(None, 1, 0, 5) == FA_ERR_INVALID_ARGUMENT
     assert {plain_check(ctypes.byref(make(**kw)), 1, 0) for kw in REJECTED} == {FA_ERR_INVALID_ARGUMENT,
                                                                                FA_ERR_UNSUPPORTED}
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_window_entries_name_the_scale_they_reject(lib, kind):
+    stem, _, make = KINDS[kind]
+    for kw in BAD_SCALES:
+        p = make(**kw)
+        for w in WINDOWS:
+            assert getattr(lib, stem + "_check")(ctypes.byref(make()), 1, 0, w) == FA_OK  # (clears the message)
+            assert getattr(lib, stem + "_check")(ctypes.byref(p), 1, 0, w) == FA_ERR_INVALID_ARGUMENT
+            assert b"softmax_scale" in lib.fa_last_error()
+            assert getattr(lib, stem)(ctypes.byref(p), 1, 0, w, None, 0, None) == FA_ERR_INVALID_ARGUMENT
 
 
 def window_plan_keys(cap, sq, w):
