@@ -401,7 +401,9 @@ def check_file(path) -> list[str]:
             return [f"{path}: no fa_decode_fp8kv kernel in the assembly (stale or wrong file)"]
         return spills(text)
     for inst, kernel in (("fa_paged_window_inst", "fa_decode_paged_window"),  # (the sliding-window variants)
-                         ("fa_paged_fp8_window_inst", "fa_decode_fp8kv_window")):
+                         ("fa_paged_fp8_window_inst", "fa_decode_fp8kv_window"),
+                         ("fa_paged_lse_inst", "fa_decode_paged_lse"),  # (the LSE variants)
+                         ("fa_paged_fp8_lse_inst", "fa_decode_fp8kv_lse")):
         if inst in str(path):
             if kernel not in text:
                 return [f"{path}: no {kernel} kernel in the assembly (stale or wrong file)"]

@@ -36,6 +36,8 @@
 // window is `if constexpr (kWindow)`. Everything is __forceinline__, so each kernel is still one flat function;
 // that the kernels do the work they did before the seam is measured, not assumed
 // (scripts/compare_decode_objs.py against the previous build, profiles/decode_unify_ab.json).
+// Two more kernels, fa_decode_paged_lse and fa_decode_fp8kv_lse (fa_decode_paged_lse.hpp), are the same body over
+// argument structs that carry an LSE output: `if constexpr (DecLse<Args>::value)` below, absent from the five.
 #include "fa_fwd_kernels.hpp"
 
 namespace fa {
@@ -61,12 +63,35 @@ struct DecGeo {
     static constexpr int kLds = kDecWaves * kWaveLds;
 };
 
+// The LSE variant (fa_decode_paged_lse.hpp): an argument struct with a member `lse` (pointer and the (batch,
+// q-head, position) element strides of an fp32 array) makes decode_body, the fused merge and the launcher also
+// write every final row's log-sum-exp. Compile-time, as the window is: the kernels whose arguments carry no
+// `lse` compile without any of it.
+template <class A, class = void>
+struct DecLse : std::false_type {};
+template <class A>
+struct DecLse<A, std::void_t<decltype(std::declval<const A &>().lse)>> : std::true_type {};
+
+// lse of row rg of (b, hkv) from the kernel's log2-unit state: ln sum_n exp(scale q.k_n) = (M + log2 L) ln 2
+// in NATURAL log units; a row without a visible key (L == 0) is -inf. (The -inf travels as its bit pattern: the
+// build is -ffinite-math-only.)
+template <class Lse>
+__device__ __forceinline__ void decode_store_lse(const fa_fwd_params &p, const Lse &o, const int g, const int b,
+                                                 const int hkv, const int rg, const float M, const float L) {
+    const int Sq = (int)p.seqlen_q;
+    const int hq = hkv * g + rg / Sq, pos = rg % Sq;
+    const float v = (M + __builtin_amdgcn_logf(L)) * 0.69314718055994531f;
+    uint32_t *dst = (uint32_t *)o.ptr + ((int64_t)b * o.batch_stride + (int64_t)hq * o.head_stride +
+                                         (int64_t)pos * o.seqlen_stride);
+    *dst = L > 0.f ? __float_as_uint(v) : 0xff800000u;
+}
+
 // Fused merge of a unit's n_split partials by the last of its workgroups (fa_decode, a.cnt): the same
 // arithmetic as fa_decode_combine (weights 2^(lse - M) in split order, acc / L), spread over the
 // workgroup: lse of every (split, row) into LDS, each row's weights by one thread, then a float4 of
 // one valid row per thread per pass. Loads are device-scope (sc1: not from this CU's L1).
-template <class DT, int kD, bool kExactD>
-__device__ __forceinline__ void decode_merge(const fa_fwd_params &p, const DecArgs &a, const int unit, const int b,
+template <class DT, int kD, bool kExactD, class A>
+__device__ __forceinline__ void decode_merge(const fa_fwd_params &p, const A &a, const int unit, const int b,
                                           const int hkv, const int rb) {
     __shared__ float wt[kDecMaxSplit][kDecRows];
     __shared__ float linv[kDecRows];
@@ -89,6 +114,7 @@ __device__ __forceinline__ void decode_merge(const fa_fwd_params &p, const DecAr
             wt[s][tid] = w;
         }
         linv[tid] = L > 0.f ? 1.f / L : 0.f;
+        if constexpr (DecLse<A>::value) decode_store_lse(p, a.lse, a.g, b, hkv, rb * kDecRows + tid, M, L);
     }
     __syncthreads();
     constexpr int C4 = kD / 4;  // float4 chunks of a row
@@ -345,8 +371,8 @@ __device__ __forceinline__ void decode_store_partial(const DecArgs &a, const Dec
 // Fused merge, the arrival: every thread's partials are in L2 before the workgroup arrives; the last
 // arrival merges the unit (the others' stores were drained before their arrivals, and its loads bypass
 // its CU's L1) and re-zeroes the counter
-template <class DT, int kD, bool kExactD>
-__device__ __forceinline__ void decode_arrive(const fa_fwd_params &p, const DecArgs &a, const DecWork &w) {
+template <class DT, int kD, bool kExactD, class A>
+__device__ __forceinline__ void decode_arrive(const fa_fwd_params &p, const A &a, const DecWork &w) {
     __shared__ uint32_t last_wg;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -632,6 +658,8 @@ __device__ __forceinline__ void decode_body(const fa_fwd_params &p, const typena
     const int rg2 = w.rb * kDecRows + row;
     if (a.n_split == 1) {
         if (rg2 < a.rows) decode_store_o<DT, kD, kExactD>(p, a, w, rg2, part, acc, inv);
+        if constexpr (DecLse<typename Kv::Args>::value)
+            if (rg2 < a.rows && part == 0) decode_store_lse(p, a.lse, a.g, w.b, w.hkv, rg2, M, L);
     } else {
         if (rg2 < a.rows) decode_store_partial<kD>(a, w, row, part, acc, inv, M, L);
         if constexpr (kFuse) decode_arrive<DT, kD, kExactD>(p, a, w);
@@ -647,8 +675,10 @@ __global__ __launch_bounds__(256, 1) void fa_decode(const fa_fwd_params p, const
 // position) row of a (batch, kv-head) -- a workgroup covers 4 of its a.rows rows, so the grid holds
 // only valid rows (B * Hkv * ceil(rows / 4) workgroups) -- lane l owns d = 2l, 2l+1 (kD = 128) or
 // d = l (kD = 64), so every partial row is one contiguous 512 / 256-B wave read.
-template <class DT, int kD, bool kExactD>
-__global__ __launch_bounds__(256) void fa_decode_combine(const fa_fwd_params p, const DecArgs a) {
+// (kLse, fa_decode_combine_lse: lane 0 also writes the row's lse to `lse`)
+struct NoLse {};
+template <class DT, int kD, bool kExactD, bool kLse, class Lse>
+__device__ __forceinline__ void decode_combine_body(const fa_fwd_params &p, const DecArgs &a, const Lse &lse) {
     constexpr int DPL = kD / 64;  // d values per lane
     const int lane = threadIdx.x & 63;
     const int nb4 = (a.rows + 3) / 4;  // workgroups per (batch, kv-head)
@@ -693,6 +723,18 @@ __global__ __launch_bounds__(256) void fa_decode_combine(const fa_fwd_params p, 
             *(uint16_t *)(orow + 2 * d) = (uint16_t)(w2 & 0xffff);
         }
     }
+    if constexpr (kLse)
+        if (lane == 0) decode_store_lse(p, lse, a.g, b, hkv, rg, M, L);
+}
+
+template <class DT, int kD, bool kExactD>
+__global__ __launch_bounds__(256) void fa_decode_combine(const fa_fwd_params p, const DecArgs a) {
+    decode_combine_body<DT, kD, kExactD, false>(p, a, NoLse{});
+}
+
+template <class DT, int kD, bool kExactD, class Lse>
+__global__ __launch_bounds__(256) void fa_decode_combine_lse(const fa_fwd_params p, const DecArgs a, const Lse lse) {
+    decode_combine_body<DT, kD, kExactD, true>(p, a, lse);
 }
 
 // The launcher of every decode kernel (`fused` / `plain`: its two instantiations; `path` / `path_split`: what
@@ -716,10 +758,15 @@ int launch_decode_kernels(const fa_fwd_params &p, Args a, void *ws, hipStream_t 
     // (fused: every XCD holds ceil(units / 8) units' splits)
     const int64_t grid = a.cnt ? 8 * ((units + 7) / 8) * a.n_split : units * a.n_split;
     hipLaunchKernelGGL(a.cnt ? fused : plain, dim3((uint32_t)grid), dim3(256), 0, stream, p, a);
-    if (a.n_split > 1 && !a.cnt)
-        hipLaunchKernelGGL((fa_decode_combine<DT, kD, kExact>),
-                           dim3((uint32_t)(p.batch_size * p.num_heads_kv * ((a.rows + 3) / 4))), dim3(256), 0, stream,
-                           p, static_cast<const DecArgs &>(a));
+    if (a.n_split > 1 && !a.cnt) {
+        const dim3 cgrid((uint32_t)(p.batch_size * p.num_heads_kv * ((a.rows + 3) / 4)));
+        if constexpr (DecLse<Args>::value)
+            hipLaunchKernelGGL((fa_decode_combine_lse<DT, kD, kExact, decltype(a.lse)>), cgrid, dim3(256), 0, stream, p,
+                               static_cast<const DecArgs &>(a), a.lse);
+        else
+            hipLaunchKernelGGL((fa_decode_combine<DT, kD, kExact>), cgrid, dim3(256), 0, stream, p,
+                               static_cast<const DecArgs &>(a));
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_err(FA_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
     set_last_path(a.n_split > 1 ? path_split : path);

@@ -71,7 +71,14 @@ struct PagedSeq : PagedWalk<kElem> {
     static __device__ __forceinline__ void key_range(const fa_fwd_params &p, const Args &a, const int b, int &k0,
                                                      int &Sk) {
         k0 = 0;
-        Sk = min(max(((len_t)a.seqlens_k)[b], 0), (int)p.seqlen_kv);
+        if constexpr (DecLse<Args>::value) {
+            // the LSE variant's length options (fa_paged_lse_launch.h): L_b = clamp(seqlens_k[b] + seqlen_offset),
+            // seqlens_k == nullptr: every sequence has clamp(seqlen_offset) keys. |seqlen_offset| <= 2^30 (host)
+            const int64_t n = (int64_t)(a.seqlens_k ? ((len_t)a.seqlens_k)[b] : 0) + a.seqlen_offset;
+            Sk = (int)(n < 0 ? 0 : n < p.seqlen_kv ? n : p.seqlen_kv);
+        } else {
+            Sk = min(max(((len_t)a.seqlens_k)[b], 0), (int)p.seqlen_kv);
+        }
     }
     static __device__ __forceinline__ int tiles_per_split(const Args &a, const int n_tiles) {
         return (n_tiles + a.n_split - 1) / a.n_split;

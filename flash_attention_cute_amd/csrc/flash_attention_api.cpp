@@ -30,6 +30,7 @@
 #include "fa_gfx950.h"
 #include "fa_gfx950_fp8.h"
 #include "fa_gfx950_kvcache.h"
+#include "fa_gfx950_lse.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_window.h"
@@ -719,6 +720,187 @@ torch::Tensor flash_attention_paged_window_fp8_fwd(torch::Tensor &q, torch::Tens
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds, window_left);
 }
 
+// Paged decode that also returns the softmax log-sum-exp (include/fa_gfx950_lse.h fa_fwd_gfx950_paged_lse /
+// _lse_fp8; the pool's dtype selects the entry): (o, lse) with lse fp32 [B, Hq, Sq] in natural log units, -inf
+// for rows without a visible key; o is bit-identical to flash_attention_paged_fwd / _fp8_fwd. Decode shapes only,
+// no window. Sequence b has clamp(cache_seqlens[b] + seqlen_offset) keys, or clamp(seqlen_offset) without
+// cache_seqlens. No q-head pack: a decode step runs as Sq 1 with g q-heads per kv-head (the same kernel rows and
+// arithmetic as the pack, causal dropped as the pack drops it), so q may be any 16-byte aligned strided view --
+// the shared-prefix decode passes a group of sequences as the positions of one batch row. `out` / `lse_out`:
+// caller-owned destinations (any strides, out 16-byte aligned), written in place; q is then never copied.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_lse_fwd(
+    torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache, torch::Tensor &block_table,
+    c10::optional<torch::Tensor> cache_seqlens, int64_t seqlen_offset, c10::optional<torch::Tensor> k_descale,
+    c10::optional<torch::Tensor> v_descale, float softmax_scale, bool causal, c10::optional<torch::Tensor> out,
+    c10::optional<torch::Tensor> lse_out) {
+    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
+                "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(q.size(3) == k_cache.size(3), "q and the caches must have the same hidden dimension");
+    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0, "q must have at least one element");
+    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
+    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
+                "number of heads in q must be multiple of number of heads in k and v");
+    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
+    const bool fp8 = k_cache.dtype() == at::kFloat8_e4m3fn;
+    if (fp8) {
+        TORCH_CHECK(v_cache.dtype() == at::kFloat8_e4m3fn, "the fp8 caches must be torch.float8_e4m3fn");
+        check_dtype(q, q, q);
+    } else {
+        TORCH_CHECK(!k_descale.has_value() && !v_descale.has_value(), "k_descale / v_descale go with an fp8 cache");
+        check_dtype(q, k_cache, v_cache);
+    }
+    TORCH_CHECK(q.stride(3) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
+                "q, k, v must be contiguous in the last dimension");
+    check_headdim_device(q, k_cache, v_cache);
+    const int64_t bs = q.size(0);
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
+                    block_table.size(1) > 0,
+                "block_table must be int32 [batch, max_pages]");
+    TORCH_CHECK(block_table.device() == q.device(), "block_table must be on the device of q");
+    TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) == 1,
+                "block_table rows must be contiguous (the table is read in place)");
+    torch::Tensor sl;
+    if (cache_seqlens.has_value()) {
+        TORCH_CHECK(cache_seqlens->dtype() == torch::kInt32 && cache_seqlens->dim() == 1 && cache_seqlens->size(0) == bs,
+                    "cache_seqlens must be int32 [batch]");
+        TORCH_CHECK(cache_seqlens->device() == q.device(), "cache_seqlens must be on the device of q");
+        sl = cache_seqlens->contiguous();
+    }
+    c10::DeviceGuard device_guard(q.device());
+    require_gfx950(q.device());
+
+    torch::Tensor qx = aligned_or_contiguous(q);
+    torch::Tensor kx = fp8 ? k_cache : aligned_or_contiguous(k_cache);
+    torch::Tensor vx = fp8 ? v_cache : aligned_or_contiguous(v_cache);
+    if (qx.size(2) == 1) causal = false;
+    torch::Tensor o;
+    if (out.has_value()) {
+        TORCH_CHECK(out->sizes() == q.sizes() && out->dtype() == q.dtype() && out->device() == q.device(),
+                    "out must have q's shape, data type and device");
+        TORCH_CHECK(out->stride(3) == 1 && aligned16(*out), "out must be 16-byte aligned, last dimension contiguous");
+        o = *out;
+    } else {
+        o = alloc_out_like(qx);
+    }
+    torch::Tensor lse;
+    if (lse_out.has_value()) {
+        TORCH_CHECK(lse_out->dim() == 3 && lse_out->size(0) == bs && lse_out->size(1) == q.size(1) &&
+                        lse_out->size(2) == q.size(2) && lse_out->dtype() == torch::kFloat32 &&
+                        lse_out->device() == q.device(),
+                    "lse_out must be fp32 [batch, heads, seqlen] on q's device");
+        lse = *lse_out;
+    } else {
+        lse = torch::empty({bs, q.size(1), q.size(2)}, q.options().dtype(torch::kFloat32));
+    }
+    TORCH_CHECK(lse.stride(0) >= 0 && lse.stride(1) >= 0 && lse.stride(2) >= 0, "lse strides must be non-negative");
+
+    fa_paged_fp8_lse_params lp8;
+    memset(&lp8, 0, sizeof(lp8));
+    fa_paged_params &pp = lp8.fp8.paged;
+    fa_fwd_params &params = pp.base;
+    fill_params(params, qx, kx, vx, o, softmax_scale);  // (k / v batch stride: the page stride)
+    params.seqlen_kv = block_table.size(1) * kx.size(2);
+    params.k_seqlen_stride = kx.stride(2);
+    params.v_seqlen_stride = vx.stride(2);
+    pp.block_table = block_table.data_ptr<int32_t>();
+    pp.block_table_stride = block_table.stride(0);
+    pp.max_pages = block_table.size(1);
+    pp.num_pages = kx.size(0);
+    pp.page_size = kx.size(2);
+    pp.seqlens_k = sl.defined() ? sl.data_ptr<int32_t>() : nullptr;
+    const int dtype = fa_dtype(qx);
+    const int c = causal ? 1 : 0;
+    if (fp8) {
+        const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr,
+                             v_descale.has_value() ? &*v_descale : nullptr};
+        torch::Tensor keep_k, keep_v;
+        fill_descales(ds, q, bs, kx.size(1), lp8.fp8.k_descale, lp8.fp8.v_descale, lp8.fp8.descale_batch_stride,
+                      lp8.fp8.descale_head_stride, keep_k, keep_v);
+        lp8.lse_ptr = lse.data_ptr<float>();
+        lp8.lse_batch_stride = lse.stride(0);
+        lp8.lse_head_stride = lse.stride(1);
+        lp8.lse_seqlen_stride = lse.stride(2);
+        lp8.seqlen_offset = seqlen_offset;
+        const int64_t ws_bytes = fa_fwd_gfx950_paged_lse_fp8_workspace_size(&lp8, dtype, c, -1);
+        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_lse_fp8_workspace_size failed: ", fa_last_error());
+        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+        check_rc(fa_fwd_gfx950_paged_lse_fp8(&lp8, dtype, c, -1, data_or_null(ws), ws_bytes, current_stream(qx)),
+                 "fa_fwd_gfx950_paged_lse_fp8");
+    } else {
+        fa_paged_lse_params lp;
+        memset(&lp, 0, sizeof(lp));
+        lp.paged = pp;
+        lp.lse_ptr = lse.data_ptr<float>();
+        lp.lse_batch_stride = lse.stride(0);
+        lp.lse_head_stride = lse.stride(1);
+        lp.lse_seqlen_stride = lse.stride(2);
+        lp.seqlen_offset = seqlen_offset;
+        const int64_t ws_bytes = fa_fwd_gfx950_paged_lse_workspace_size(&lp, dtype, c, -1);
+        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_lse_workspace_size failed: ", fa_last_error());
+        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+        check_rc(fa_fwd_gfx950_paged_lse(&lp, dtype, c, -1, data_or_null(ws), ws_bytes, current_stream(qx)),
+                 "fa_fwd_gfx950_paged_lse");
+    }
+    return {o, lse};
+}
+
+// Merge of partial attention states (include/fa_gfx950_lse.h fa_merge_states_gfx950): outs [N, B, H, S, D]
+// fp16 / bf16 and lses [N, B, H, S] fp32 (any strides; outs copied only if not 16-byte aligned) -> (out
+// [B, H, S, D], lse [B, H, S] or an empty tensor). One HIP pass.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states(torch::Tensor &outs, torch::Tensor &lses,
+                                                                      bool return_lse) {
+    TORCH_CHECK(outs.dim() == 5 && lses.dim() == 4, "outs must be [parts, batch, heads, seqlen, dim], lses "
+                "[parts, batch, heads, seqlen]");
+    TORCH_CHECK(outs.sizes().slice(0, 4) == lses.sizes(), "outs and lses must agree in their first four dimensions");
+    TORCH_CHECK(outs.dtype() == torch::kHalf || outs.dtype() == torch::kBFloat16, "outs only support fp16 or bf16");
+    TORCH_CHECK(lses.dtype() == torch::kFloat32, "lses must be fp32");
+    TORCH_CHECK(outs.size(0) >= 1, "at least one partial state is needed");
+    TORCH_CHECK(outs.size(4) > 0 && outs.size(4) % 8 == 0, "hidden dimension must be multiple of 8");
+    TORCH_CHECK(outs.is_cuda() && lses.is_cuda() && outs.device() == lses.device(),
+                "outs and lses must be on the same CUDA device");
+    c10::DeviceGuard device_guard(outs.device());
+    require_gfx950(outs.device());
+    bool ok = outs.stride(4) == 1 && reinterpret_cast<uintptr_t>(outs.data_ptr()) % 16 == 0;
+    for (int i = 0; i < 4; ++i) ok = ok && (outs.size(i) == 1 || (outs.stride(i) >= 0 && outs.stride(i) % 8 == 0));
+    torch::Tensor ox = ok ? outs : outs.contiguous();
+    bool lok = true;
+    for (int i = 0; i < 4; ++i) lok = lok && (lses.size(i) == 1 || lses.stride(i) >= 0);
+    torch::Tensor lx = lok ? lses : lses.contiguous();
+    auto o = torch::empty({ox.size(1), ox.size(2), ox.size(3), ox.size(4)}, ox.options());
+    torch::Tensor lse = return_lse ? torch::empty({ox.size(1), ox.size(2), ox.size(3)}, lx.options()) : torch::Tensor();
+    fa_merge_params mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.outs = ox.data_ptr();
+    mp.lses = lx.data_ptr<float>();
+    mp.out = o.data_ptr();
+    mp.lse = return_lse ? lse.data_ptr<float>() : nullptr;
+    mp.num_parts = ox.size(0);
+    mp.batch_size = ox.size(1);
+    mp.num_heads = ox.size(2);
+    mp.seqlen = ox.size(3);
+    mp.headdim = ox.size(4);
+    mp.outs_part_stride = stride_or_zero(ox, 0);
+    mp.outs_batch_stride = stride_or_zero(ox, 1);
+    mp.outs_head_stride = stride_or_zero(ox, 2);
+    mp.outs_seqlen_stride = stride_or_zero(ox, 3);
+    mp.lses_part_stride = stride_or_zero(lx, 0);
+    mp.lses_batch_stride = stride_or_zero(lx, 1);
+    mp.lses_head_stride = stride_or_zero(lx, 2);
+    mp.lses_seqlen_stride = stride_or_zero(lx, 3);
+    mp.out_batch_stride = stride_or_zero(o, 0);
+    mp.out_head_stride = stride_or_zero(o, 1);
+    mp.out_seqlen_stride = stride_or_zero(o, 2);
+    if (return_lse) {
+        mp.lse_batch_stride = stride_or_zero(lse, 0);
+        mp.lse_head_stride = stride_or_zero(lse, 1);
+        mp.lse_seqlen_stride = stride_or_zero(lse, 2);
+    }
+    check_rc(fa_merge_states_gfx950(&mp, ox.dtype() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16, current_stream(ox)),
+             "fa_merge_states_gfx950");
+    return {o, return_lse ? lse : torch::empty({0}, lx.options())};
+}
+
 // In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
 // k / v [B, Hkv, Sn, D] are written at positions cache_seqlens[b] + i of the paged ([num_pages, Hkv,
 // page_size, D] + block_table int32 [B, max_pages]) or dense ([B, Hkv, Smax, D], no table) cache, k rotated
@@ -946,4 +1128,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_paged_prefill_fwd", &flash_attention::flash_attention_paged_prefill_fwd,
           "Prefill-sized query blocks over a 16-bit paged KV cache read in place (page_size % 64 == 0), gfx950");
     m.def("paged_prefill_version", []() { return fa_paged_prefill_version(); });
+    m.def("flash_attention_paged_lse_fwd", &flash_attention::flash_attention_paged_lse_fwd,
+          "Paged decode (16-bit or FP8 pool) that also returns the softmax log-sum-exp, gfx950");
+    m.def("flash_attention_merge_states", &flash_attention::flash_attention_merge_states,
+          "Merge partial attention states (outputs and log-sum-exps over disjoint key sets), one HIP pass (gfx950)");
+    m.def("lse_version", []() { return fa_lse_version(); });
 }

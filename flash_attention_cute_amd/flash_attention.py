@@ -508,7 +508,7 @@ def flash_attention_paged_window_forward_fake(q, k_cache, v_cache, block_table, 
 
 
 def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False,
-                          k_descale=None, v_descale=None, window_left=-1):
+                          k_descale=None, v_descale=None, window_left=-1, return_lse=False):
     """Attention of q [B, Hq, Sq, D] -- each sequence's LAST Sq positions -- over a paged KV cache:
     ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] with any strides (flash-attn's
     [num_pages, page_size, Hkv, D] is ``cache.transpose(1, 2)``), ``page_size`` a multiple of 32;
@@ -542,9 +542,19 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     below ``max(0, L_b - Sq - window_left) // 64 * 64`` and their entries are never read). The copying path
     passes the window to ``flash_attn_padded_func`` (it gathers every page of the table, so there the entries
     of freed pages must still be valid to clamp). ``window_left < 0``
-    (the default) is no window: the call above, bit for bit."""
+    (the default) is no window: the call above, bit for bit.
+
+    ``return_lse=True`` returns ``(out, lse)``: ``lse`` fp32 [B, Hq, Sq], the natural-log
+    ``ln sum_n exp(softmax_scale * q . k_n)`` over each row's visible keys (flash-attn's ``softmax_lse``; with an
+    FP8 cache the scale includes ``k_descale``, ``v_descale`` does not enter), ``-inf`` for a row without a
+    visible key. ``out`` is bit-identical to the call without it. Decode shapes only and no window
+    (``NotImplementedError`` otherwise), D a multiple of 8. Two such results over disjoint key sets combine
+    with ``flash_attn_merge_states``. The default runs the unchanged call."""
     softmax_scale = _default_scale(q, softmax_scale)
     window_left = int(window_left)
+    if return_lse:
+        return _paged_lse(q, k_cache, v_cache, block_table, cache_seqlens, 0, softmax_scale, causal, k_descale,
+                          v_descale, window_left)
     if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
         b, hkv = q.size(0), k_cache.size(1)
         kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
@@ -672,7 +682,8 @@ def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
                             cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
-                            return_seqlens=False, k_descale=None, v_descale=None, window_left=-1):
+                            return_seqlens=False, k_descale=None, v_descale=None, window_left=-1,
+                            shared_prefix_len=0):
     """flash-attn's ``flash_attn_with_kvcache`` in this project's [B, H, S, D] layout: one serving step on
     a paged (``block_table`` given) or dense KV cache. When ``k`` / ``v`` [B, Hkv, Sn, D] are given they are
     appended in place at ``cache_seqlens`` (``flash_attn_kvcache_append``: the same drop rules); when the
@@ -695,8 +706,21 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     FP8 cache through its identity table, the windowed paged kernel never reads the pages below the window. On
     a dense 16-bit cache a decode step (``Sq == 1``) folds the window into its key range on the device,
     ``[max(new_seqlens - 1 - window_left, 0), new_seqlens)``, and runs the split-KV decode kernel; ``Sq > 1``
-    passes the window to ``flash_attn_padded_func``. Still no host synchronisation."""
+    passes the window to ``flash_attn_padded_func``. Still no host synchronisation.
+
+    ``shared_prefix_len > 0`` runs the attention half as ``flash_attn_paged_shared_prefix_func(...,
+    prefix_len=shared_prefix_len)`` over the advanced lengths (its contract applies): paged caches only, decode
+    steps (``Sq == 1``) only, no window (``ValueError`` otherwise); the append is unchanged. The default 0 is the
+    call above, bit for bit."""
     window_left = int(window_left)
+    shared_prefix_len = int(shared_prefix_len)
+    if shared_prefix_len:
+        if block_table is None:
+            raise ValueError("shared_prefix_len applies to a paged cache (block_table) only")
+        if q.size(2) != 1:
+            raise ValueError(f"shared_prefix_len applies to decode steps (Sq == 1) only (got Sq = {q.size(2)})")
+        if window_left >= 0:
+            raise ValueError("shared_prefix_len and window_left cannot be combined")
     if cache_seqlens is None:
         raise ValueError("flash_attn_with_kvcache needs cache_seqlens (int32 [batch])")
     if (k is None) != (v is None):
@@ -722,7 +746,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         table = block_table
         if table is None:  # a dense cache: batch row b is page b
             table = torch.arange(b, dtype=torch.int32, device=q.device)[:, None]
-        if window_left >= 0:
+        if shared_prefix_len:
+            out = flash_attn_paged_shared_prefix_func(q_rot, k_cache, v_cache, table, new_seqlens, shared_prefix_len,
+                                                      softmax_scale, causal, kd, vd)
+        elif window_left >= 0:
             out = torch.ops.flash_attention.paged_window_forward_fp8(q_rot, k_cache, v_cache, table, new_seqlens,
                                                                      window_left, kd, vd, softmax_scale, causal)
         else:
@@ -734,7 +761,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
             k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos.to(q.dtype), rotary_sin.to(q.dtype))
     elif k is not None:
         new_seqlens, _ = torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table)
-    if block_table is not None:
+    if shared_prefix_len:
+        out = flash_attn_paged_shared_prefix_func(q_rot, k_cache, v_cache, block_table, new_seqlens, shared_prefix_len,
+                                                  softmax_scale, causal)
+    elif block_table is not None:
         out = flash_attn_paged_func(q_rot, k_cache, v_cache, block_table, new_seqlens, softmax_scale, causal,
                                     window_left=window_left)
     elif window_left >= 0 and q.size(2) == 1:
@@ -959,3 +989,314 @@ def flash_attention_kvcache_append_fp8_fake(k_cache, v_cache, k, v, cache_seqlen
     q_rot = (torch.empty(0, dtype=_io_dtype(k, q), device=k_cache.device) if q is None
              else torch.empty(q.shape, dtype=q.dtype, device=q.device))
     return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format), q_rot
+
+
+# ---------------------------------------------------------------------------------------------
+# LSE output, state merge and shared-prefix decode on the paged cache (include/fa_gfx950_lse.h); no
+# reference counterpart. The LSE is flash-attn's ``softmax_lse`` (natural log), the merge vLLM's
+# ``merge_attn_states`` / flashinfer's ``merge_state``: attention results over DISJOINT key sets combine
+# exactly, which is what shared-prefix (cascade) decode and sequence-sharded decode are built from.
+# ---------------------------------------------------------------------------------------------
+_SHARED_PREFIX_GROUP_ROWS = 32  # (q-head, sequence) rows of one prefix-phase group: g * c (one 32-row block)
+
+
+def _paged_lse_reference(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, k_descale, v_descale,
+                         softmax_scale, causal):
+    """The non-GPU default of the LSE ops, a float restatement: (o, lse) with the kernel's semantics (lengths
+    ``clamp(cache_seqlens[b] + seqlen_offset)`` or ``clamp(seqlen_offset)``, bottom-right causal per sequence, GQA,
+    rows without a visible key o = 0 and lse = -inf; FP8: k_descale in the scale, v_descale on o)."""
+    b_, hq, sq, d = q.shape
+    num_pages, hkv, page_size, _ = k_cache.shape
+    g = hq // hkv
+    cap = block_table.size(1) * page_size
+    scale = d ** -0.5 if softmax_scale is None else softmax_scale
+    lens = cache_seqlens.tolist() if cache_seqlens is not None else [0] * b_
+    out = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+    lse = torch.full((b_, hq, sq), float("-inf"), dtype=torch.float32, device=q.device)
+    for b, n in enumerate(lens):
+        n = min(max(n + seqlen_offset, 0), cap)
+        if n == 0:
+            continue
+        ids = block_table[b, :(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
+        kb = k_cache.index_select(0, ids).float().transpose(0, 1).flatten(1, 2)[:, :n].repeat_interleave(g, dim=0)
+        vb = v_cache.index_select(0, ids).float().transpose(0, 1).flatten(1, 2)[:, :n].repeat_interleave(g, dim=0)
+        s = torch.matmul(q[b].float(), kb.transpose(1, 2)) * scale  # [Hq, Sq, n]
+        if k_descale is not None:
+            s = s * k_descale[b].float().repeat_interleave(g)[:, None, None]
+        if causal:
+            s = s.masked_fill(~_bottom_right_causal(sq, n, q.device)[None], float("-inf"))
+        l = torch.logsumexp(s, dim=-1)
+        p = torch.exp(s - l.masked_fill(l == float("-inf"), 0)[..., None])
+        o = torch.matmul(p, vb)
+        if v_descale is not None:
+            o = o * v_descale[b].float().repeat_interleave(g)[:, None, None]
+        out[b], lse[b] = o, l
+    return out.to(q.dtype), lse
+
+
+def _paged_lse_cuda(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, k_descale, v_descale,
+                    softmax_scale, causal, out=None, lse=None):
+    _require_ext()
+    if block_table.stride(1) != 1 and block_table.size(1) > 1:  # (rows are read in place: a row is contiguous)
+        block_table = block_table.contiguous()
+    return flash_attention_cuda.flash_attention_paged_lse_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), k_cache, v_cache, block_table, cache_seqlens, int(seqlen_offset),
+        k_descale, v_descale, softmax_scale, causal, out, lse)
+
+
+@torch.library.custom_op("flash_attention::paged_forward_lse", mutates_args=())
+def flash_attention_paged_forward_lse(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                      block_table: torch.Tensor, cache_seqlens: Optional[torch.Tensor],
+                                      seqlen_offset: int = 0, softmax_scale: float = None,
+                                      causal: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    # paged_forward that also returns lse fp32 [B, Hq, Sq] (natural log; -inf for rows without a visible key);
+    # sequence b has clamp(cache_seqlens[b] + seqlen_offset) keys, clamp(seqlen_offset) without cache_seqlens.
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _paged_lse_reference(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, None, None,
+                                softmax_scale, causal)
+
+
+@torch.library.register_kernel("flash_attention::paged_forward_lse", "cuda")
+def flash_attention_paged_forward_lse_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                           block_table: torch.Tensor, cache_seqlens: Optional[torch.Tensor],
+                                           seqlen_offset: int = 0, softmax_scale: float = None,
+                                           causal: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    o, lse = _paged_lse_cuda(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, None, None,
+                             softmax_scale, causal)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::paged_forward_lse")
+def flash_attention_paged_forward_lse_fake(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset=0,
+                                           softmax_scale=None, causal=False):
+    return torch.empty_like(q), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
+@torch.library.custom_op("flash_attention::paged_forward_lse_fp8", mutates_args=())
+def flash_attention_paged_forward_lse_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                          block_table: torch.Tensor, cache_seqlens: Optional[torch.Tensor],
+                                          k_descale: Optional[torch.Tensor] = None,
+                                          v_descale: Optional[torch.Tensor] = None, seqlen_offset: int = 0,
+                                          softmax_scale: float = None,
+                                          causal: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _paged_lse_reference(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, k_descale, v_descale,
+                                softmax_scale, causal)
+
+
+@torch.library.register_kernel("flash_attention::paged_forward_lse_fp8", "cuda")
+def flash_attention_paged_forward_lse_fp8_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                               block_table: torch.Tensor, cache_seqlens: Optional[torch.Tensor],
+                                               k_descale: Optional[torch.Tensor] = None,
+                                               v_descale: Optional[torch.Tensor] = None, seqlen_offset: int = 0,
+                                               softmax_scale: float = None,
+                                               causal: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    o, lse = _paged_lse_cuda(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, k_descale, v_descale,
+                             softmax_scale, causal)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::paged_forward_lse_fp8")
+def flash_attention_paged_forward_lse_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, k_descale=None,
+                                               v_descale=None, seqlen_offset=0, softmax_scale=None, causal=False):
+    return torch.empty_like(q), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
+def _check_lse_shape(q, k_cache, window_left):
+    """The wrapper errors of every LSE call: the LSE kernels serve decode shapes without a window."""
+    if window_left >= 0:
+        raise NotImplementedError("the sliding-window decode kernels have no LSE variant (window_left >= 0)")
+    g, sq = q.size(1) // k_cache.size(1), q.size(2)
+    if g * sq > _PAGED_DECODE_MAX_ROWS:
+        raise NotImplementedError(f"the LSE is returned for decode shapes only (Hq / Hkv * Sq <= "
+                                  f"{_PAGED_DECODE_MAX_ROWS}, got {g * sq}): the prefill kernels have no LSE variant")
+    if q.size(3) % 8 != 0:
+        raise NotImplementedError(f"the LSE calls need a head dim that is a multiple of 8 (got {q.size(3)})")
+
+
+def _paged_lse(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset, softmax_scale, causal, k_descale,
+               v_descale, window_left):
+    _check_lse_shape(q, k_cache, window_left)
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        b, hkv = q.size(0), k_cache.size(1)
+        kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
+        vd = _descale_arg(v_descale, "v_descale", b, hkv, q.device)
+        return torch.ops.flash_attention.paged_forward_lse_fp8(q, k_cache, v_cache, block_table, cache_seqlens, kd, vd,
+                                                               seqlen_offset, softmax_scale, causal)
+    return torch.ops.flash_attention.paged_forward_lse(q, k_cache, v_cache, block_table, cache_seqlens, seqlen_offset,
+                                                       softmax_scale, causal)
+
+
+def _merge_reference(outs, lses, return_lse):
+    """The non-GPU default of merge_states, a float restatement of the kernel's rule."""
+    mx = lses.max(dim=0).values
+    w = torch.exp(lses - mx.masked_fill(mx == float("-inf"), 0))  # (a -inf part weighs 0)
+    sw = w.sum(dim=0)
+    o = (w[..., None] * outs.float()).sum(dim=0) / sw.masked_fill(sw == 0, 1)[..., None]
+    o = o.masked_fill((sw == 0)[..., None], 0).to(outs.dtype)
+    lse = mx + torch.log(sw)  # (all -inf: -inf + log 0 = -inf)
+    return o, (lse.masked_fill(sw == 0, float("-inf")) if return_lse else lses.new_empty(0))
+
+
+@torch.library.custom_op("flash_attention::merge_states", mutates_args=())
+def flash_attention_merge_states(outs: torch.Tensor, lses: torch.Tensor,
+                                 return_lse: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    # outs [N, B, H, S, D] fp16 / bf16, lses [N, B, H, S] fp32 -> (out [B, H, S, D], lse [B, H, S] or empty)
+    return _merge_reference(outs, lses, return_lse)
+
+
+@torch.library.register_kernel("flash_attention::merge_states", "cuda")
+def flash_attention_merge_states_cuda(outs: torch.Tensor, lses: torch.Tensor,
+                                      return_lse: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_merge_states(outs, lses, return_lse)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::merge_states")
+def flash_attention_merge_states_fake(outs, lses, return_lse=False):
+    return (outs.new_empty(outs.shape[1:]),
+            lses.new_empty(lses.shape[1:]) if return_lse else lses.new_empty(0))
+
+
+def flash_attn_merge_states(outs, lses, return_lse=False):
+    """Merge N partial attention states over DISJOINT key sets: ``outs`` [N, B, Hq, Sq, D] (fp16 / bf16, D a
+    multiple of 8) and ``lses`` [N, B, Hq, Sq] (fp32, natural log, as ``flash_attn_paged_func(return_lse=True)``
+    returns them), as tensors of any strides or as sequences of N tensors (stacked: a copy). Per row,
+    ``w_i = exp(lse_i - max_i lse_i)``, ``out = sum_i w_i o_i / sum_i w_i`` in fp32 rounded once, ``lse = max_i lse_i
+    + ln sum_i w_i``; a part with ``lse = -inf`` weighs 0 and a row whose parts all are gives 0 and ``-inf``.
+    1 <= N <= 16. One memory-bound HIP pass, no host synchronisation (graph-capturable). Returns ``out`` or
+    ``(out, lse)``."""
+    if not isinstance(outs, torch.Tensor):
+        outs = torch.stack(list(outs))
+    if not isinstance(lses, torch.Tensor):
+        lses = torch.stack(list(lses))
+    if outs.dim() != 5 or lses.dim() != 4 or outs.shape[:4] != lses.shape:
+        raise ValueError(f"outs must be [N, B, Hq, Sq, D] and lses [N, B, Hq, Sq] (got {tuple(outs.shape)} and "
+                         f"{tuple(lses.shape)})")
+    if not 1 <= outs.size(0) <= 16:
+        raise ValueError(f"1 to 16 partial states can be merged (got {outs.size(0)})")
+    if outs.size(4) % 8 != 0:
+        raise ValueError(f"the head dim must be a multiple of 8 (got {outs.size(4)})")
+    if lses.dtype != torch.float32:
+        raise ValueError(f"lses must be fp32 (got {lses.dtype})")
+    o, lse = torch.ops.flash_attention.merge_states(outs, lses, return_lse)
+    return (o, lse) if return_lse else o
+
+
+def _check_shared_prefix_enabled() -> bool:
+    """FA_CHECK_SHARED_PREFIX, read at every call (as FA_CHECK_VARLEN is)."""
+    return os.environ.get("FA_CHECK_SHARED_PREFIX", "0") not in ("", "0")
+
+
+def _check_shared_prefix_table(block_table, n_pre, groups):
+    """Raise if the rows of a group differ in their prefix entries (FA_CHECK_SHARED_PREFIX=1; one host read)."""
+    bad = []
+    for lo, hi in groups:
+        rows = block_table[lo:hi, :n_pre]
+        bad.append((rows != rows[:1]).any())
+    if bool(torch.stack(bad).any()):
+        raise ValueError("flash_attn_paged_shared_prefix_func: the sequences of a group must carry the same page ids "
+                         "in their first prefix_len / page_size block-table entries")
+
+
+def _lse_into(q, k_cache, v_cache, table, seqlens, offset, kd, vd, scale, causal, out, lse):
+    """One LSE decode launch that writes o / lse through the given (strided) views."""
+    if q.is_cuda:
+        _paged_lse_cuda(q, k_cache, v_cache, table, seqlens, offset, kd, vd, scale, causal, out, lse)
+    else:
+        o, l = _paged_lse_reference(q, k_cache, v_cache, table, seqlens, offset, kd, vd, scale, causal)
+        out.copy_(o)
+        lse.copy_(l)
+
+
+def flash_attn_paged_shared_prefix_func(q, k_cache, v_cache, block_table, cache_seqlens, prefix_len,
+                                        softmax_scale=None, causal=False, k_descale=None, v_descale=None,
+                                        return_lse=False, _group_rows=None):
+    """A decode step (q [B, Hq, 1, D]) of ``flash_attn_paged_func`` for a batch whose sequences SHARE their first
+    ``prefix_len`` keys (a system prompt, few-shot examples, a prefix-cache hit, beam or parallel sampling): the
+    shared pages are streamed once per GROUP of sequences instead of once per sequence. 16-bit and FP8 pools.
+
+    The caller's contract:
+
+    * ``prefix_len`` is a Python int and a multiple of ``page_size`` (``ValueError`` otherwise), at most the
+      table's capacity;
+    * every sequence holds at least ``prefix_len`` keys; a shorter ``cache_seqlens[b]`` is treated as exactly
+      ``prefix_len`` (its suffix clamps to 0 keys);
+    * sequences are grouped ``c = max(1, 32 // (Hq / Hkv))`` at a time in batch order (rows ``[i c, (i + 1) c)``,
+      the last group may be shorter); the rows of one group carry the same page ids in their first
+      ``prefix_len / page_size`` table entries and, with an FP8 cache, the same descales. So a batch in which
+      EVERY sequence shares the prefix qualifies, as does one sorted so that each group does;
+    * ``FA_CHECK_SHARED_PREFIX=1`` (read per call, eager only, off by default) verifies the table condition
+      with one host read and raises ``ValueError``.
+
+    Three launches, four when ``B % c != 0``; no copies, no helper kernels, no host synchronisation
+    (graph-capturable). Prefix phase: each group is ONE batch row of the LSE decode kernel -- q viewed in place
+    as [B / c, Hq, c, D], the table ``block_table[::c, :prefix_len / page_size]``, every row ``prefix_len`` keys,
+    non-causal. Suffix phase: the LSE decode kernel over ``block_table[:, prefix_len / page_size:]`` with
+    ``cache_seqlens - prefix_len`` keys (the offset is applied in the kernel). Then ``flash_attn_merge_states``.
+
+    What is never read: the prefix table entries of every row but a group's first; in the prefix phase, entries
+    at or past ``prefix_len / page_size``.
+
+    The result differs from ``flash_attn_paged_func`` on the same table by rounding only (the two partial
+    outputs are rounded to q's dtype before the merge). ``prefix_len == 0`` IS ``flash_attn_paged_func``, bit for
+    bit. ``return_lse=True`` also returns the merged lse. It is an explicit call: nothing dispatches to it; it
+    pays off for long prefixes and many sequences (DESIGN.md section 5 has the measured crossover).
+    ``Sq > 1`` raises ``ValueError`` (the (sequence, position) rows of a group are not one strided view)."""
+    prefix_len = int(prefix_len)
+    page_size = k_cache.size(2)
+    if prefix_len < 0 or prefix_len % page_size != 0:
+        raise ValueError(f"prefix_len ({prefix_len}) must be a non-negative multiple of page_size ({page_size})")
+    if q.dim() != 4 or q.size(2) != 1:
+        raise ValueError(f"shared-prefix decode serves decode steps (q [B, Hq, 1, D]) only (got {tuple(q.shape)})")
+    if prefix_len == 0:
+        return flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal,
+                                     k_descale, v_descale, return_lse=return_lse)
+    n_pre = prefix_len // page_size
+    if n_pre > block_table.size(1):
+        raise ValueError(f"prefix_len ({prefix_len}) exceeds the block table's capacity "
+                         f"({block_table.size(1) * page_size})")
+    softmax_scale = _default_scale(q, softmax_scale)
+    _check_lse_shape(q, k_cache, -1)
+    b, hq, _, d = q.shape
+    hkv = k_cache.size(1)
+    g = hq // hkv
+    kd = vd = None
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
+        vd = _descale_arg(v_descale, "v_descale", b, hkv, q.device)
+    rows = _SHARED_PREFIX_GROUP_ROWS if _group_rows is None else int(_group_rows)
+    c = max(1, min(rows, _PAGED_DECODE_MAX_ROWS) // g)
+    n_full = b // c
+    groups = [(i * c, (i + 1) * c) for i in range(n_full)] + ([(n_full * c, b)] if b % c else [])
+    if _check_shared_prefix_enabled() and not torch.compiler.is_compiling() and not (
+            q.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check_shared_prefix_table(block_table, n_pre, groups)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if block_table.stride(1) != 1:
+        block_table = block_table.contiguous()
+
+    # the two states: [0] the prefix phase, [1] the suffix phase
+    outs = torch.empty((2, b, hq, 1, d), dtype=q.dtype, device=q.device)
+    lses = torch.empty((2, b, hq, 1), dtype=torch.float32, device=q.device)
+    # prefix phase: rows [lo, lo + n * cc) as n batch rows of cc positions, each group's first table row
+    for lo, n, cc in ((0, n_full, c), (n_full * c, 1, b % c)):
+        if n == 0 or cc == 0:
+            continue
+        qv = q.as_strided((n, hq, cc, d), (cc * q.stride(0), q.stride(1), q.stride(0), 1),
+                          q.storage_offset() + lo * q.stride(0))
+        ov = outs.as_strided((n, hq, cc, d), (cc * hq * d, d, hq * d, 1), lo * hq * d)
+        lv = lses.as_strided((n, hq, cc), (cc * hq, 1, hq), lo * hq)
+        hi = lo + n * cc
+        _lse_into(qv, k_cache, v_cache, block_table[lo:hi:cc, :n_pre], None, prefix_len,
+                  None if kd is None else kd[lo:hi:cc], None if vd is None else vd[lo:hi:cc], softmax_scale, False,
+                  ov, lv)
+    # suffix phase: every sequence's own keys (a table without suffix columns: 0 keys, no entry is read)
+    if n_pre < block_table.size(1):
+        table, lens, off = block_table[:, n_pre:], cache_seqlens, -prefix_len
+    else:
+        table, lens, off = block_table[:, :1], None, 0
+    _lse_into(q, k_cache, v_cache, table, lens, off, kd, vd, softmax_scale, causal, outs[1], lses[1])
+    return flash_attn_merge_states(outs, lses, return_lse)
