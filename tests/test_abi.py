@@ -24,6 +24,13 @@ class FaFwdParams(ctypes.Structure):
                 + [("softmax_scale", ctypes.c_float)])
 
 
+class FaRopeFwdParams(ctypes.Structure):
+    """include/fa_gfx950.h ``fa_rope_fwd_params``."""
+
+    _fields_ = [("base", FaFwdParams), ("rope_cos", ctypes.c_void_p), ("rope_sin", ctypes.c_void_p),
+                ("rope_batch_stride", ctypes.c_int64), ("rope_seqlen_stride", ctypes.c_int64)]
+
+
 def declared_functions() -> list[str]:
     text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
     return re.findall(r"\b(fa_\w+)\s*\(", text)
@@ -124,10 +131,6 @@ def test_every_dense_entry_rejects_a_scale_that_is_not_finite_and_positive(lib, 
     lib.fa_fwd_gfx950_padded.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.fa_fwd_gfx950_padded_workspace_size.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
-
-    class FaRopeFwdParams(ctypes.Structure):
-        _fields_ = [("base", FaFwdParams), ("rope_cos", ctypes.c_void_p), ("rope_sin", ctypes.c_void_p),
-                    ("rope_batch_stride", ctypes.c_int64), ("rope_seqlen_stride", ctypes.c_int64)]
 
     for base in (good_params(softmax_scale=scale), decode_params()):
         base.softmax_scale = scale

@@ -292,7 +292,10 @@ def test_padded_prefill_seqlen_sliced_q(padded_op, device, causal):
 def test_padded_out_of_range_positions_are_clamped(padded_op, device):
     """Ranges past the tensors (negative starts, ends past Sq / Sk, end < start) are clamped on the
     device (include/fa_gfx950.h): the result equals the call with the clamped ranges, and nothing
-    outside the output tensor is written (guard rows around it stay untouched)."""
+    outside q / k / v is READ (they sit between NaN guard rows inside one allocation, and the output stays
+    finite). The output here is the op's own fresh allocation, so this test does not see what is written
+    outside it: tests/test_footprint.py::test_padded_out_of_range_positions_are_clamped_with_a_guarded_output
+    runs the clamp case with the output between guard bands."""
     b, hq, hkv, s, d = 4, 8, 2, 300, 128
     q, k, v = make_batch(b, hq, hkv, s, s, d, torch.bfloat16, 23, "bhsd")
     bad = [torch.tensor(x, dtype=torch.int32) for x in
