@@ -36,6 +36,11 @@ from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond th
     flash_attention_paged_window_forward,
     flash_attention_paged_window_forward_fp8,
 )
+from flash_attention_cute_amd.flash_attention import (  # noqa: F401  (beyond the reference: ragged step on the paged cache)
+    flash_attn_kvcache_append_varlen,
+    flash_attn_paged_varlen_func,
+    flash_attn_varlen_with_kvcache,
+)
 
 from .load_cpp_extention import load_extension  # noqa: F401  (the reference module imports it, :2)
 

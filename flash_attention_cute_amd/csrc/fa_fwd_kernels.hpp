@@ -889,6 +889,15 @@ constexpr int vmcnt_enc(int n) { return (n & 15) | (((n >> 4) & 3) << 14) | 0x70
 #ifndef FA_W4_PAGED
 #define FA_W4_PAGED 0
 #endif
+// FA_W4_PAGED_VARLEN (fa_paged_varlen.hpp sets it, with FA_W4_PAGED, to 1): the paged kernel with RAGGED
+// queries -- it takes a PagedVarlenArgs and every Q block's rows from cu_seqlens_q (q_rows_of). Translation
+// units of its own, so that the uniform paged kernel and the dense kernels preprocess to what they were.
+#ifndef FA_W4_PAGED_VARLEN
+#define FA_W4_PAGED_VARLEN 0
+#endif
+#if FA_W4_PAGED_VARLEN && !FA_W4_PAGED
+#error "FA_W4_PAGED_VARLEN needs FA_W4_PAGED"
+#endif
 #if FA_W4_PAGED
 // Where the K / V tiles of one Q block of sequence b live. A page holds tpp whole 64-key tiles, so tile t is
 // tile t % tpp of page row[t / tpp]. The pipelined loop issues K tile j + 1 and V tile j in iteration j --
@@ -967,7 +976,13 @@ struct PagedTiles {
 // has been drained.
 // =============================================================================================
 template <class DT, bool kCausal, int kD, bool kExactD>
-#if FA_W4_PAGED
+#if FA_W4_PAGED_VARLEN  // (the same name, another argument struct: an overload the ragged translation units hold)
+__global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
+                                                          unsigned long long *stamps, const PathArgs xa,
+                                                          const PagedVarlenArgs pv) {
+    const PagedPrefillArgs pg = pv.paged;
+    const int total_q = pv.total_q;
+#elif FA_W4_PAGED
 __global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
                                                           unsigned long long *stamps, const PathArgs xa,
                                                           const PagedPrefillArgs pg) {
@@ -1230,11 +1245,30 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     pt.tpp = pg.tiles_per_page;
     pt.last_page = pg.num_pages - 1;
 #endif
+#if FA_W4_PAGED_VARLEN
+    // the packed query rows [q0, q0 + result) of sequence b (xa.q_rng = cu_seqlens_q, rng_hi = 1): q0 =
+    // clamp(cu[b], 0, total_q), the end clamped into [q0, total_q], so a bad array never addresses outside q / o.
+    // The index is made wave-uniform: the loads stay scalar and the block's descriptors stay in SGPRs.
+    auto q_rows_of = [&](const int b, int &q0) __attribute__((always_inline)) {
+        const int bu = __builtin_amdgcn_readfirstlane(b);
+        q0 = min(max(xa.q_rng[bu], 0), total_q);
+        return min(max(xa.q_rng[bu + xa.rng_hi], q0), total_q) - q0;
+    };
+#endif
     auto set_block = [&](const Work wk) {
         const int hq = hp ? 4 * wk.hq + wave : wk.hq, b = wk.b;  // (hp: wk.hq is the q-head quad)
         const int hkv = hq / (int)p.head_q_per_group;
         int64_t qrow0 = (int64_t)b * p.q_batch_stride, krow0 = (int64_t)b * p.k_batch_stride;
         int64_t vrow0 = (int64_t)b * p.v_batch_stride, orow0 = (int64_t)b * p.o_batch_stride;
+#if FA_W4_PAGED_VARLEN
+        {   // ragged queries: this sequence's packed rows (q_rows_of: both bounds clamped into [0, total_q]). No
+            // key range: the keys come from the table, and Sk, diag and n_blocks from the paged block below
+            int q0;
+            Sq = q_rows_of(b, q0);
+            qrow0 = (int64_t)q0 * p.q_seqlen_stride;
+            orow0 = (int64_t)q0 * p.o_seqlen_stride;
+        }
+#else
         if (xa.q_rng) {  // this batch row's query rows and keys: absolute rows (the host zeroes the
                          // batch strides of ranged tensors; both ranges are given together here)
             const int q0 = xa.q_rng[b], k0 = xa.k_rng[b];
@@ -1247,6 +1281,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
             krow0 = (int64_t)k0 * p.k_seqlen_stride;
             vrow0 = (int64_t)k0 * p.v_seqlen_stride;
         }
+#endif
 #if FA_W4_PAGED
         {   // this sequence's keys: its length clamped to the table's capacity (p.seqlen_kv), its tiles through
             // its block-table row (kb / vb below: the pool at this kv-head; the batch stride is the PAGE stride)
@@ -1378,11 +1413,19 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     auto q_rsrc_of = [&](const Work wk, int &rb) __attribute__((always_inline)) {
         int64_t row0 = (int64_t)wk.b * p.q_batch_stride;
         int sq = (int)p.seqlen_q;
+#if FA_W4_PAGED_VARLEN
+        {
+            int q0;
+            sq = q_rows_of(wk.b, q0);
+            row0 = (int64_t)q0 * qs_;
+        }
+#else
         if (xa.q_rng) {
             const int q0 = xa.q_rng[wk.b];
             sq = xa.q_rng[wk.b + xa.rng_hi] - q0;
             row0 = (int64_t)q0 * qs_;
         }
+#endif
         int m0n;
         geom_of(qtile_of(wk), sq, m0n, rb);
         const int mwn = hp ? m0n : m0n + wave * 32;

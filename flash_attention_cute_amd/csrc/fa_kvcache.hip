@@ -16,90 +16,21 @@
 #include <stdint.h>
 
 #include "fa_gfx950_kvcache.h"
+#include "fa_kvcache_move.h"
 #include "fa_launch.h"
 
 namespace fa {
 namespace {
 
-typedef uint32_t u32x4k __attribute__((ext_vector_type(4)));
-typedef float f2k __attribute__((ext_vector_type(2)));
-
-template <bool kF16>
-__device__ __forceinline__ float ld(const uint16_t v) {
-    if constexpr (kF16) return (float)__builtin_bit_cast(_Float16, v);
-    else return (float)__builtin_bit_cast(__bf16, v);
-}
-template <bool kF16>
-__device__ __forceinline__ uint16_t st(const float f) {
-    if constexpr (kF16) return __builtin_bit_cast(uint16_t, (_Float16)f);
-    else return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
-template <bool kF16>
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-    if constexpr (kF16) {
-        typedef _Float16 hh2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector((f2k){lo, hi}, hh2));
-    } else {
-        typedef __bf16 bb2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector((f2k){lo, hi}, bb2));
-    }
-}
-
-// thread mappings: kVec 16-B chunk pairs (d0, d0 + D/2), D % 16 == 0, everything 16-B aligned;
-// kPair element pairs (d0, d0 + D/2), any even D; kElem single elements (no tables, any D)
-enum Mode { kVec = 0, kPair = 1, kElem = 2 };
-
-// the chunk pair of fa_rope_kernel<kF16, true>: rotates when cs != nullptr, else copies
-template <bool kF16>
-__device__ __forceinline__ void move_vec(const uint16_t *x, uint16_t *o, const uint16_t *cs, const uint16_t *sn,
-                                         const int d0, const int d1) {
-    const u32x4k xa = *(const u32x4k *)(x + d0), xb = *(const u32x4k *)(x + d1);
-    if (!cs) {
-        *(u32x4k *)(o + d0) = xa;
-        *(u32x4k *)(o + d1) = xb;
-        return;
-    }
-    const u32x4k ca = *(const u32x4k *)(cs + d0), cb = *(const u32x4k *)(cs + d1);
-    const u32x4k sa = *(const u32x4k *)(sn + d0), sb = *(const u32x4k *)(sn + d1);
-    const uint16_t *xa_ = (const uint16_t *)&xa, *xb_ = (const uint16_t *)&xb;
-    const uint16_t *ca_ = (const uint16_t *)&ca, *cb_ = (const uint16_t *)&cb;
-    const uint16_t *sa_ = (const uint16_t *)&sa, *sb_ = (const uint16_t *)&sb;
-    u32x4k oa, ob;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float a[2], bb[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int e = 2 * j + t;
-            const float u = ld<kF16>(xa_[e]), w = ld<kF16>(xb_[e]);
-            a[t] = __builtin_fmaf(u, ld<kF16>(ca_[e]), -w * ld<kF16>(sa_[e]));
-            bb[t] = __builtin_fmaf(w, ld<kF16>(cb_[e]), u * ld<kF16>(sb_[e]));
-        }
-        asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(bb[0]), "+v"(bb[1]));  // fp32 step kept (fa_rope.hip)
-        oa[j] = pack2<kF16>(a[0], a[1]);
-        ob[j] = pack2<kF16>(bb[0], bb[1]);
-    }
-    *(u32x4k *)(o + d0) = oa;
-    *(u32x4k *)(o + d1) = ob;
-}
-
-// the element pair of fa_rope_kernel<kF16, false>
-template <bool kF16>
-__device__ __forceinline__ void move_pair(const uint16_t *x, uint16_t *o, const uint16_t *cs, const uint16_t *sn,
-                                          const int d0, const int d1) {
-    if (!cs) {
-        o[d0] = x[d0];
-        o[d1] = x[d1];
-        return;
-    }
-    const float u = ld<kF16>(x[d0]), w = ld<kF16>(x[d1]);
-    float a = __builtin_fmaf(u, ld<kF16>(cs[d0]), -w * ld<kF16>(sn[d0]));
-    float bb = __builtin_fmaf(w, ld<kF16>(cs[d1]), u * ld<kF16>(sn[d1]));
-    // keep the fp32 rounding step (fa_rope.hip: without the pin hipcc folds it into a mixed-precision fma)
-    asm volatile("" : "+v"(a), "+v"(bb));
-    o[d0] = st<kF16>(a);
-    o[d1] = st<kF16>(bb);
-}
+// ld / st / pack2, Mode, move_vec, move_pair: fa_kvcache_move.h, shared with fa_kvcache_varlen.hip. The movers
+// keep fa_rope.hip's fp32 pin there, the line
+//     asm volatile("" : "+v"(a), "+v"(bb));
+// between the fma and the one rounding (without it hipcc folds the step into a mixed-precision fma).
+// KEEP THE QUOTED LINE: tests/test_kvcache_abi.py (test_kvcache_source_is_a_translation_unit_of_its_own) looks for
+// it in THIS file, as it did when the movers were defined here. Since they moved, that assertion checks this
+// comment and no longer code; the code is checked by tests/test_kvcache_varlen_abi.py
+// (test_both_append_kernels_share_one_definition_of_the_movers) and, bit for bit, by the GPU append tests.
+using namespace kvmove;
 
 // items: [0, n_kv) K rows, [n_kv, 2 n_kv) V rows, [2 n_kv, 2 n_kv + n_q) q rows, each (b, h, s, chunk)
 // row-major. Threads [0, B) of the launch also write seqlens_out (the launch has at least B items).
@@ -168,30 +99,20 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(const fa_kvcache
     }
 }
 
-bool al16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
-
-int per_row_of(const fa_kvcache_params &p, int mode) {
-    return (int)(mode == kVec ? p.headdim / 16 : mode == kPair ? p.headdim / 2 : p.headdim);
-}
-
 // the 16-B path needs every chunk of every tensor the launch touches 16-B aligned
 int pick_mode(const fa_kvcache_params &p) {
     bool vec = p.headdim % 16 == 0;
-    if (p.seqlen_new > 0) {
-        const int64_t st[12] = {p.kn_batch_stride, p.kn_head_stride, p.kn_seqlen_stride, p.vn_batch_stride,
-                                p.vn_head_stride,  p.vn_seqlen_stride, p.k_page_stride,  p.k_head_stride,
-                                p.k_row_stride,    p.v_page_stride,    p.v_head_stride,  p.v_row_stride};
-        for (int i = 0; i < 12; ++i) vec = vec && st[i] % 8 == 0;
-        vec = vec && al16(p.k_new) && al16(p.v_new) && al16(p.k_cache) && al16(p.v_cache);
-    }
-    if (p.seqlen_q > 0) {
-        const int64_t st[6] = {p.q_batch_stride,  p.q_head_stride,  p.q_seqlen_stride,
-                               p.qo_batch_stride, p.qo_head_stride, p.qo_seqlen_stride};
-        for (int i = 0; i < 6; ++i) vec = vec && st[i] % 8 == 0;
-        vec = vec && al16(p.q) && al16(p.q_out);
-    }
-    if (p.cos) vec = vec && p.cs_row_stride % 8 == 0 && al16(p.cos) && al16(p.sin);
-    return vec ? kVec : p.headdim % 2 == 0 ? kPair : kElem;
+    if (p.seqlen_new > 0)
+        vec = vec && vec_ok({p.kn_batch_stride, p.kn_head_stride, p.kn_seqlen_stride, p.vn_batch_stride,
+                             p.vn_head_stride, p.vn_seqlen_stride, p.k_page_stride, p.k_head_stride, p.k_row_stride,
+                             p.v_page_stride, p.v_head_stride, p.v_row_stride},
+                            {p.k_new, p.v_new, p.k_cache, p.v_cache});
+    if (p.seqlen_q > 0)
+        vec = vec && vec_ok({p.q_batch_stride, p.q_head_stride, p.q_seqlen_stride, p.qo_batch_stride,
+                             p.qo_head_stride, p.qo_seqlen_stride},
+                            {p.q, p.q_out});
+    if (p.cos) vec = vec && vec_ok({p.cs_row_stride}, {p.cos, p.sin});
+    return mode_of(vec, p.headdim);
 }
 
 }  // namespace
@@ -236,18 +157,9 @@ int kvcache_check(const fa_kvcache_params *p, int dtype) {
                            "num_heads_q (%lld) must be a positive multiple of num_heads_kv (%lld)",
                            (long long)p->num_heads_q, (long long)p->num_heads_kv);
     }
-    if (p->cos) {
-        if (p->headdim & 1) return set_err(FA_ERR_INVALID_ARGUMENT, "RoPE needs an even head dim (got %lld)",
-                                           (long long)p->headdim);
-        if (p->max_pos < 1) return set_err(FA_ERR_INVALID_ARGUMENT, "max_pos must be at least 1 (the tables' rows)");
-    }
-    if (p->seqlens_out) {
-        const uintptr_t a = (uintptr_t)p->seqlens_k, b = (uintptr_t)p->seqlens_out;
-        const uintptr_t n = (uintptr_t)p->batch_size * 4;
-        if ((a <= b ? b - a : a - b) < n)  // (the distance, so nothing wraps at the ends of the address space)
-            return set_err(FA_ERR_INVALID_ARGUMENT,
-                           "seqlens_out must not overlap seqlens_k (the launch is still reading it)");
-    }
+    if (const int rc = kvmove::check_tables_and_lengths(p->cos, p->headdim, p->max_pos, p->seqlens_k,
+                                                        p->seqlens_out, p->batch_size))
+        return rc;
     // one thread per item (at most headdim per row), 256 per workgroup, a 1-D grid
     if ((double)p->batch_size * (2.0 * p->num_heads_kv * p->seqlen_new + (double)p->num_heads_q * p->seqlen_q) *
             (double)p->headdim > 0x7fffffffLL * 256.0)
@@ -260,7 +172,7 @@ int kvcache_launch(const fa_kvcache_params *p, int dtype, hipStream_t stream) {
     if (rc != FA_OK) return rc;
     if (p->batch_size == 0 || (p->seqlen_new == 0 && p->seqlen_q == 0)) return FA_OK;
     const int mode = pick_mode(*p);
-    const int per_row = per_row_of(*p, mode);
+    const int per_row = per_row_of(p->headdim, mode);
     const int64_t n_kv = p->batch_size * p->num_heads_kv * p->seqlen_new * per_row;
     const int64_t items = 2 * n_kv + p->batch_size * p->num_heads_q * p->seqlen_q * per_row;
     const dim3 grid((uint32_t)((items + 255) / 256));

@@ -30,9 +30,11 @@
 #include "fa_gfx950.h"
 #include "fa_gfx950_fp8.h"
 #include "fa_gfx950_kvcache.h"
+#include "fa_gfx950_kvcache_varlen.h"
 #include "fa_gfx950_lse.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
+#include "fa_gfx950_paged_varlen.h"
 #include "fa_gfx950_paged_window.h"
 
 namespace flash_attention {
@@ -1094,6 +1096,237 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_fp8(
     return kvcache_append_impl(k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin, &ds);
 }
 
+// Ragged queries over a 16-bit paged cache (include/fa_gfx950_paged_varlen.h fa_fwd_gfx950_paged_varlen): q packed
+// [total_q, Hq, D] with cu_seqlens_q int32 [B + 1] on the device, sequence b's rows its last positions over
+// cache_seqlens[b] keys; the pool read in place by the paged fa_fwd_w4 (page_size a multiple of 64). q is read in
+// place when its row and head strides are multiples of 8 and its base is 16-byte aligned (a slice of a fused QKV
+// projection), else made contiguous, as flash_attention_varlen_fwd does. No host synchronisation.
+torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                               torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q,
+                                               torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                               int64_t window_left, float softmax_scale, bool causal) {
+    TORCH_CHECK(q.dim() == 3, "ragged q must be 3-D [total_q, heads, dim]");
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4, "the caches must be 4-D [pages, heads, page_size, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(q.size(2) == k_cache.size(3), "q and the caches must have the same hidden dimension");
+    TORCH_CHECK(q.size(1) > 0 && q.size(2) > 0, "q must have at least one head and one element per row");
+    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
+    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
+                "number of heads in q must be multiple of number of heads in k and v");
+    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 64 == 0, "page_size must be a positive multiple of 64");
+    check_dtype(q, k_cache, v_cache);
+    TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
+                "q, k, v must be contiguous in the last dimension");
+    check_headdim_device(q, k_cache, v_cache);
+    TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32 && cu_seqlens_q.dim() == 1 && cu_seqlens_q.size(0) >= 1,
+                "cu_seqlens_q must be int32 with batch_size + 1 entries");
+    const int64_t bs = cu_seqlens_q.size(0) - 1;
+    TORCH_CHECK(cu_seqlens_q.device() == q.device(), "cu_seqlens_q must be on the device of q");
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
+                    block_table.size(1) > 0,
+                "block_table must be int32 [batch, max_pages]");
+    TORCH_CHECK(block_table.device() == q.device(), "block_table must be on the device of q");
+    TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) == 1,
+                "block_table rows must be contiguous (the table is read in place)");
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
+                "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(cache_seqlens.device() == q.device(), "cache_seqlens must be on the device of q");
+    TORCH_CHECK(max_seqlen_q >= 0, "max_seqlen_q must be non-negative");
+    c10::DeviceGuard device_guard(q.device());
+    require_gfx950(q.device());
+
+    auto o = torch::empty_like(q);
+    // nothing to launch: no row, no q-tile, or an empty step (batch 0, as the append and the C ABI take it)
+    if (q.size(0) == 0 || max_seqlen_q == 0 || bs == 0) return o;
+    auto aligned_rows = [](const torch::Tensor &t) {
+        return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && (t.stride(0) % 8 == 0 || t.size(0) <= 1) &&
+               (t.stride(1) % 8 == 0 || t.size(1) <= 1);
+    };
+    torch::Tensor qx = aligned_rows(q) ? q : q.contiguous();
+    if (!aligned_rows(o) || o.stride(2) != 1) o = torch::empty(q.sizes(), q.options());
+    torch::Tensor kx = aligned_or_contiguous(k_cache), vx = aligned_or_contiguous(v_cache);
+    torch::Tensor cq = cu_seqlens_q.contiguous(), sl = cache_seqlens.contiguous();
+
+    fa_paged_varlen_params vp;
+    memset(&vp, 0, sizeof(vp));
+    fa_paged_params &pp = vp.paged;
+    fa_fwd_params &params = pp.base;
+    params.q_ptr = qx.data_ptr();
+    params.k_ptr = kx.data_ptr();
+    params.v_ptr = vx.data_ptr();
+    params.o_ptr = o.data_ptr();
+    params.batch_size = bs;
+    params.num_heads_q = qx.size(1);
+    params.num_heads_kv = kx.size(1);
+    params.seqlen_q = max_seqlen_q;
+    params.seqlen_kv = block_table.size(1) * kx.size(2);
+    params.headdim = qx.size(2);
+    params.head_q_per_group = qx.size(1) / kx.size(1);
+    params.q_head_stride = qx.size(1) == 1 ? 0 : qx.stride(1);
+    params.o_head_stride = o.size(1) == 1 ? 0 : o.stride(1);
+    params.q_seqlen_stride = qx.size(0) == 1 ? qx.size(1) * qx.size(2) : qx.stride(0);
+    params.o_seqlen_stride = o.size(0) == 1 ? o.size(1) * o.size(2) : o.stride(0);
+    params.k_batch_stride = stride_or_zero(kx, 0);  // (the page stride)
+    params.v_batch_stride = stride_or_zero(vx, 0);
+    params.k_head_stride = stride_or_zero(kx, 1);
+    params.v_head_stride = stride_or_zero(vx, 1);
+    params.k_seqlen_stride = kx.stride(2);
+    params.v_seqlen_stride = vx.stride(2);
+    softmax_scale *= M_LOG2E;
+    params.softmax_scale = softmax_scale;
+    pp.block_table = block_table.data_ptr<int32_t>();
+    pp.block_table_stride = block_table.stride(0);
+    pp.max_pages = block_table.size(1);
+    pp.num_pages = kx.size(0);
+    pp.page_size = kx.size(2);
+    pp.seqlens_k = sl.data_ptr<int32_t>();
+    vp.cu_seqlens_q = cq.data_ptr<int32_t>();
+    vp.total_q = qx.size(0);
+    const int dtype = fa_dtype(qx);
+    const int64_t ws_bytes = fa_fwd_gfx950_paged_varlen_workspace_size(&vp, dtype, causal ? 1 : 0, window_left);
+    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_varlen_workspace_size failed: ", fa_last_error());
+    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
+    check_rc(fa_fwd_gfx950_paged_varlen(&vp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
+                                        current_stream(qx)),
+             "fa_fwd_gfx950_paged_varlen");
+    return o;
+}
+
+// Ragged in-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache_varlen.h
+// fa_kvcache_append_varlen_gfx950): k / v packed [total_new, Hkv, D] with cu_seqlens_new int32 [B + 1], token i of
+// sequence b written at position cache_seqlens[b] + i of the paged 16-bit cache; q packed [total_q, Hq, D] with
+// its own cu_seqlens_q rotated at the sequence's last positions after the append. Returns (new_seqlens int32 [B],
+// q_rot or an empty tensor). One launch, nothing copied, no host synchronisation (graph-capturable).
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
+    torch::Tensor &k_cache, torch::Tensor &v_cache, torch::Tensor &k, torch::Tensor &v, torch::Tensor &cu_seqlens_new,
+    torch::Tensor &cache_seqlens, torch::Tensor &block_table, c10::optional<torch::Tensor> rotary_cos,
+    c10::optional<torch::Tensor> rotary_sin, c10::optional<torch::Tensor> q,
+    c10::optional<torch::Tensor> cu_seqlens_q) {
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4, "the caches must be 4-D [pages, heads, page_size, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(k_cache.dtype() == v_cache.dtype(), "k_cache, v_cache must have the same data type");
+    TORCH_CHECK(k_cache.dtype() == torch::kHalf || k_cache.dtype() == torch::kBFloat16,
+                "the caches only support fp16 or bf16 data type");
+    TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.device() == v_cache.device(),
+                "the caches must be on the same CUDA device");
+    TORCH_CHECK(k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
+                "the caches must be contiguous in the last dimension (they are written in place, never copied)");
+    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0 && k_cache.size(3) > 0 && k_cache.size(2) > 0 &&
+                    k_cache.size(2) % 32 == 0,
+                "the caches need at least one page and one head, and page_size a positive multiple of 32");
+    TORCH_CHECK(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be given together");
+    TORCH_CHECK(!q.has_value() || rotary_cos.has_value(), "q is rotated only: it needs rotary_cos / rotary_sin");
+    TORCH_CHECK(q.has_value() == cu_seqlens_q.has_value(), "q and cu_seqlens_q must be given together");
+    const auto dev = k_cache.device();
+    const int64_t bs = cache_seqlens.dim() == 1 ? cache_seqlens.size(0) : -1;
+    const int64_t hkv = k_cache.size(1), d = k_cache.size(3);
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && bs >= 0, "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(cache_seqlens.device() == dev, "cache_seqlens must be on the device of the caches");
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
+                    block_table.size(1) > 0,
+                "block_table must be int32 [batch, max_pages]");
+    TORCH_CHECK(block_table.device() == dev, "block_table must be on the device of the caches");
+    auto check_cu = [&](const torch::Tensor &t, const char *name) {
+        TORCH_CHECK(t.dtype() == torch::kInt32 && t.dim() == 1 && t.size(0) == bs + 1, name,
+                    " must be int32 with batch + 1 entries");
+        TORCH_CHECK(t.device() == dev, name, " must be on the device of the caches");
+    };
+    auto check_rows = [&](const torch::Tensor &t, const char *name, int64_t heads_multiple_of) {
+        TORCH_CHECK(t.dim() == 3 && t.size(2) == d, name, " must be [total, heads, dim] with the caches' hidden dimension");
+        TORCH_CHECK(t.size(1) > 0 && t.size(1) % heads_multiple_of == 0, name, ": wrong number of heads");
+        TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+        TORCH_CHECK(t.device() == dev, name, " must be on the device of the caches");
+        TORCH_CHECK(t.stride(2) == 1, name, " must be contiguous in the last dimension");
+    };
+    check_cu(cu_seqlens_new, "cu_seqlens_new");
+    check_rows(k, "k", hkv);
+    check_rows(v, "v", hkv);
+    TORCH_CHECK(k.size(1) == hkv && k.sizes() == v.sizes(), "k, v must have the caches' number of heads");
+    if (q.has_value()) {
+        check_cu(*cu_seqlens_q, "cu_seqlens_q");
+        check_rows(*q, "q", hkv);
+    }
+    torch::Tensor cs, sn_t;
+    if (rotary_cos.has_value()) {
+        TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
+        auto table = [&](const torch::Tensor &t, const char *name) {
+            TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
+            TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
+            TORCH_CHECK(t.device() == dev, name, " must be on the device of the caches");
+            return t.stride(1) == 1 ? t : t.contiguous();
+        };
+        cs = table(*rotary_cos, "rotary_cos");
+        sn_t = table(*rotary_sin, "rotary_sin");
+        TORCH_CHECK(cs.size(0) == sn_t.size(0), "rotary_cos and rotary_sin must have the same number of rows");
+        if (cs.size(0) > 1 && cs.stride(0) != sn_t.stride(0)) {
+            cs = cs.contiguous();
+            sn_t = sn_t.contiguous();
+        }
+    }
+    c10::DeviceGuard device_guard(dev);
+    require_gfx950(dev);
+
+    const int64_t tn = k.size(0), tq = q.has_value() ? q->size(0) : 0;
+    torch::Tensor q_rot = q.has_value() ? torch::empty(q->sizes(), q->options()) : torch::empty({0}, k_cache.options());
+    torch::Tensor sl = cache_seqlens.contiguous();
+    torch::Tensor new_seqlens = torch::empty({bs}, sl.options());
+    if (bs == 0) return {new_seqlens, q_rot};
+    torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
+    torch::Tensor cn = cu_seqlens_new.contiguous(), cq;
+
+    fa_kvcache_varlen_params p;
+    memset(&p, 0, sizeof(p));
+    p.cu_seqlens_new = cn.data_ptr<int32_t>();
+    p.total_new = tn;
+    if (tn > 0) {
+        p.k_new = k.data_ptr();
+        p.v_new = v.data_ptr();
+        p.kn_row_stride = stride_or_zero(k, 0);
+        p.kn_head_stride = stride_or_zero(k, 1);
+        p.vn_row_stride = stride_or_zero(v, 0);
+        p.vn_head_stride = stride_or_zero(v, 1);
+    }
+    if (tq > 0) {
+        cq = cu_seqlens_q->contiguous();
+        p.cu_seqlens_q = cq.data_ptr<int32_t>();
+        p.total_q = tq;
+        p.q = q->data_ptr();
+        p.q_out = q_rot.data_ptr();
+        p.q_row_stride = stride_or_zero(*q, 0);
+        p.q_head_stride = stride_or_zero(*q, 1);
+        p.qo_row_stride = stride_or_zero(q_rot, 0);
+        p.qo_head_stride = stride_or_zero(q_rot, 1);
+        p.num_heads_q = q->size(1);
+    }
+    if (cs.defined()) {
+        p.cos = cs.data_ptr();
+        p.sin = sn_t.data_ptr();
+        p.cs_row_stride = stride_or_zero(cs, 0);
+        p.max_pos = cs.size(0);
+    }
+    p.k_cache = k_cache.data_ptr();
+    p.v_cache = v_cache.data_ptr();
+    p.k_page_stride = stride_or_zero(k_cache, 0);
+    p.k_head_stride = stride_or_zero(k_cache, 1);
+    p.k_row_stride = stride_or_zero(k_cache, 2);
+    p.v_page_stride = stride_or_zero(v_cache, 0);
+    p.v_head_stride = stride_or_zero(v_cache, 1);
+    p.v_row_stride = stride_or_zero(v_cache, 2);
+    p.block_table = bt.data_ptr<int32_t>();
+    p.block_table_stride = bt.stride(0);
+    p.max_pages = bt.size(1);
+    p.num_pages = k_cache.size(0);
+    p.page_size = k_cache.size(2);
+    p.seqlens_k = sl.data_ptr<int32_t>();
+    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
+    p.batch_size = bs;
+    p.num_heads_kv = hkv;
+    p.headdim = d;
+    check_rc(fa_kvcache_append_varlen_gfx950(&p, fa_dtype(k_cache), current_stream(k_cache)),
+             "fa_kvcache_append_varlen_gfx950");
+    return {new_seqlens, q_rot};
+}
+
 }  // namespace flash_attention
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1133,4 +1366,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_merge_states", &flash_attention::flash_attention_merge_states,
           "Merge partial attention states (outputs and log-sum-exps over disjoint key sets), one HIP pass (gfx950)");
     m.def("lse_version", []() { return fa_lse_version(); });
+    m.def("flash_attention_paged_varlen_fwd", &flash_attention::flash_attention_paged_varlen_fwd,
+          "Ragged (packed, cu_seqlens_q) query blocks over a 16-bit paged KV cache read in place, gfx950");
+    m.def("paged_varlen_version", []() { return fa_paged_varlen_version(); });
+    m.def("flash_attention_kvcache_append_varlen", &flash_attention::flash_attention_kvcache_append_varlen,
+          "Ragged in-place append to a paged KV cache with fused rotate-half RoPE of k and q, one HIP launch (gfx950)");
+    m.def("kvcache_varlen_version", []() { return fa_kvcache_varlen_version(); });
 }

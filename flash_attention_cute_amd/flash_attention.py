@@ -1300,3 +1300,274 @@ def flash_attn_paged_shared_prefix_func(q, k_cache, v_cache, block_table, cache_
         table, lens, off = block_table[:, :1], None, 0
     _lse_into(q, k_cache, v_cache, table, lens, off, kd, vd, softmax_scale, causal, outs[1], lses[1])
     return flash_attn_merge_states(outs, lses, return_lse)
+
+
+# ---------------------------------------------------------------------------------------------
+# Ragged queries and a ragged append on the paged cache -- one step of a continuous batch
+# (include/fa_gfx950_paged_varlen.h fa_fwd_gfx950_paged_varlen, include/fa_gfx950_kvcache_varlen.h
+# fa_kvcache_append_varlen_gfx950); no reference counterpart. flash-attn's packed layout: q [total_q, Hq, D]
+# with cu_seqlens_q, sequence b's rows its LAST Sq_b positions over cache_seqlens[b] keys of the page pool
+# -- what flash_attn_varlen_func(..., block_table=...) gives an engine. New ops beside the uniform ones,
+# whose schemas stay as they are.
+# ---------------------------------------------------------------------------------------------
+def _clamped_ranges(cu: torch.Tensor, total: int):
+    """[(r0, r1)] per sequence, clamped as the kernels clamp a cumulative array: r0 into [0, total], r1 into
+    [r0, total]."""
+    c = cu.tolist()
+    out = []
+    for b in range(len(c) - 1):
+        r0 = min(max(c[b], 0), total)
+        out.append((r0, min(max(c[b + 1], r0), total)))
+    return out
+
+
+def _paged_varlen_unsupported(q, k_cache, v_cache):
+    """The layouts the ragged paged kernel does not read, with the alternative to use instead."""
+    alt = ("call flash_attn_paged_func once per chunk length, or gather the pages into packed keys for "
+           "flash_attn_varlen_func")
+    if k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE:
+        raise NotImplementedError(f"flash_attn_paged_varlen_func does not read FP8 pools: {alt}")
+    if k_cache.size(2) % _PAGED_PREFILL_TILE != 0:
+        raise NotImplementedError(f"flash_attn_paged_varlen_func needs page_size ({k_cache.size(2)}) to be a multiple "
+                                  f"of {_PAGED_PREFILL_TILE}: {alt}")
+    if q.size(-1) % 8 != 0:
+        raise NotImplementedError(f"flash_attn_paged_varlen_func needs a head dim ({q.size(-1)}) that is a multiple "
+                                  f"of 8: {alt}")
+
+
+@torch.library.custom_op("flash_attention::paged_varlen_forward", mutates_args=())
+def flash_attention_paged_varlen_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                         cu_seqlens_q: torch.Tensor, max_seqlen_q: int, block_table: torch.Tensor,
+                                         cache_seqlens: torch.Tensor, softmax_scale: float = None,
+                                         causal: bool = False, window_left: int = -1) -> torch.Tensor:
+    # q: [total_q, Hq, D] packed; caches: [num_pages, Hkv, page_size, D]; cu_seqlens_q: int32 [B + 1];
+    # block_table: int32 [B, max_pages]; cache_seqlens: int32 [B]. Non-GPU default: a per-sequence loop in the
+    # style of _paged_reference (the sequence's pages gathered, torch SDPA under the kernel's masks, rows with
+    # no visible key 0, both arrays clamped as the kernel clamps them).
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    window_left = min(int(window_left), _MAX_WINDOW)
+    out = torch.zeros_like(q)
+    num_pages, _, page_size, _ = k_cache.shape
+    cap = block_table.size(1) * page_size
+    lens = cache_seqlens.tolist()
+    for b, (q0, q1) in enumerate(_clamped_ranges(cu_seqlens_q, q.size(0))):
+        n, sq = min(max(lens[b], 0), cap), q1 - q0
+        if n == 0 or sq == 0:
+            continue
+        first = max(0, n - sq - window_left) // page_size if window_left >= 0 else 0  # the first page read
+        k0 = first * page_size
+        ids = block_table[b, first:(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
+        kb = k_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n - k0]
+        vb = v_cache.index_select(0, ids).transpose(0, 1).flatten(1, 2)[None, :, :n - k0]
+        if window_left >= 0:
+            mask = _window_mask(sq, n, window_left, causal, q.device)[:, k0:]
+        else:
+            mask = _bottom_right_causal(sq, n, q.device) if causal else None
+        out[q0:q1] = _masked_sdpa(q[q0:q1].transpose(0, 1)[None], kb, vb, mask, softmax_scale)[0].transpose(0, 1)
+    return out
+
+
+@torch.library.register_kernel("flash_attention::paged_varlen_forward", "cuda")
+def flash_attention_paged_varlen_forward_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                              cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                                              block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                              softmax_scale: float = None, causal: bool = False,
+                                              window_left: int = -1) -> torch.Tensor:
+    _require_ext()
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    return flash_attention_cuda.flash_attention_paged_varlen_fwd(
+        q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), block_table, cache_seqlens,
+        min(int(window_left), _MAX_WINDOW), softmax_scale, causal)
+
+
+@torch.library.register_fake("flash_attention::paged_varlen_forward")
+def flash_attention_paged_varlen_forward_fake(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                              cache_seqlens, softmax_scale=None, causal=False, window_left=-1):
+    return torch.empty_like(q)
+
+
+def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens,
+                                 softmax_scale=None, causal=False, window_left=-1):
+    """Attention of RAGGED query blocks over a paged KV cache, in one launch: ``q`` [total_q, Hq, D] packed
+    (flash-attn's varlen layout), sequence b owning rows ``[cu_seqlens_q[b], cu_seqlens_q[b + 1])`` (int32
+    [B + 1] on q's device) -- its LAST ``Sq_b`` positions over ``L_b = clamp(cache_seqlens[b], 0, max_pages *
+    page_size)`` keys of the pools ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] (any strides) named by
+    ``block_table`` int32 [B, max_pages], as in ``flash_attn_paged_func``. Returns ``out`` [total_q, Hq, D].
+
+    Masks are per sequence: key n is visible to query m iff ``window_left < 0 or n >= m + L_b - Sq_b -
+    window_left`` and, with ``causal``, ``n <= m + L_b - Sq_b``. Rows that see no key are 0; ``Sq_b == 0`` and
+    ``L_b == 0`` are valid. Rows of ``out`` outside ``[cu_seqlens_q[0], cu_seqlens_q[B])`` are unspecified.
+
+    ``q`` is read in place when its row and head strides are multiples of 8 and its base is 16-byte aligned (a
+    slice of a fused QKV projection); other layouts are made contiguous. ``max_seqlen_q`` (a host int) sizes
+    the grid and must be at least the true maximum ``Sq_b``; a larger value only launches empty q-tiles, a
+    smaller one leaves rows uncomputed. ``FA_CHECK_VARLEN=1`` in the environment verifies it (one host sync).
+
+    On the device both bounds of a sequence are clamped into ``[0, total_q]`` (the second to at least the first),
+    so a bad ``cu_seqlens_q`` never reads or writes outside ``q`` / ``out``; page ids are clamped into the pool
+    and lengths to the table's capacity. Per sequence, with its own ``Sq_b``: table entries at or past
+    ``ceil(L_b / page_size)`` are never read, and with a window the PAGES WHOLLY BELOW ``max(0, L_b - Sq_b -
+    window_left) // 64 * 64``, AND THEIR TABLE ENTRIES, ARE NEVER READ. The result is bit-identical to
+    ``flash_attn_varlen_func`` on the gathered keys packed densely. No host synchronisation (graph-capturable).
+
+    This is the paged PREFILL kernel: every sequence costs at least one 256-row block per q-head, so A
+    ONE-TOKEN SEQUENCE COSTS A WHOLE 256-ROW BLOCK. An engine should send its pure decode sequences to
+    ``flash_attn_paged_func`` and only the sequences with prompt chunks here. 16-bit pools with ``page_size`` a
+    multiple of 64 and D a multiple of 8 only (``NotImplementedError`` otherwise: call ``flash_attn_paged_func``
+    once per chunk length, or gather the pages for ``flash_attn_varlen_func``)."""
+    softmax_scale = _default_scale(q, softmax_scale)
+    if _check_varlen_enabled():
+        longest = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max()) if cu_seqlens_q.numel() > 1 else 0
+        if longest > int(max_seqlen_q):
+            raise ValueError(f"max_seqlen_q={int(max_seqlen_q)} is smaller than the longest sequence ({longest}) "
+                             "in cu_seqlens_q")
+    return torch.ops.flash_attention.paged_varlen_forward(q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q),
+                                                          block_table, cache_seqlens, softmax_scale, causal,
+                                                          int(window_left))
+
+
+@torch.library.custom_op("flash_attention::kvcache_append_varlen", mutates_args=("k_cache", "v_cache"))
+def flash_attention_kvcache_append_varlen(k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor,
+                                          v: torch.Tensor, cu_seqlens_new: torch.Tensor, cache_seqlens: torch.Tensor,
+                                          block_table: torch.Tensor, rotary_cos: Optional[torch.Tensor] = None,
+                                          rotary_sin: Optional[torch.Tensor] = None,
+                                          q: Optional[torch.Tensor] = None,
+                                          cu_seqlens_q: Optional[torch.Tensor] = None
+                                          ) -> tuple[torch.Tensor, torch.Tensor]:
+    # caches: [num_pages, Hkv, page_size, D] with block_table int32 [B, max_pages]; k, v: [total_new, Hkv, D]
+    # packed with cu_seqlens_new int32 [B + 1]; q: [total_q, Hq, D] with cu_seqlens_q (or None); rotary_*:
+    # [max_pos, D]. Non-GPU default: the kernel's semantics token by token, with the same drop rules.
+    if q is not None and rotary_cos is None:
+        raise ValueError("q is rotated only: it needs rotary_cos / rotary_sin")
+    if (q is None) != (cu_seqlens_q is None):
+        raise ValueError("q and cu_seqlens_q must be given together")
+    if k_cache.dtype == FP8_DTYPE:
+        raise NotImplementedError("flash_attn_kvcache_append_varlen writes 16-bit paged caches only: use "
+                                  "flash_attn_kvcache_append per chunk length for an FP8 cache")
+    num_pages, _, page_size, _ = k_cache.shape
+    cap = block_table.size(1) * page_size
+    lens = [min(max(n, 0), cap) for n in cache_seqlens.tolist()]
+    new_rng = _clamped_ranges(cu_seqlens_new, k.size(0))
+    new_lens = [min(n + r1 - r0, cap) for n, (r0, r1) in zip(lens, new_rng)]
+    table = block_table.tolist()
+    rope = rotary_cos is not None
+    if rope:
+        cos, sin = rotary_cos.to(k_cache.dtype), rotary_sin.to(k_cache.dtype)
+        max_pos = cos.size(0)
+    for b, (r0, r1) in enumerate(new_rng):
+        for i in range(r1 - r0):
+            n = lens[b] + i
+            if n >= cap:
+                continue  # past the table's capacity: dropped
+            page = table[b][n // page_size]
+            if page < 0 or page >= num_pages:
+                continue  # outside the pool: dropped, never clamped
+            kr = k[r0 + i][None, :, None]
+            if rope:
+                pos = min(n, max_pos - 1)
+                kr = _rope_reference(kr, cos[pos:pos + 1], sin[pos:pos + 1])
+            k_cache[page, :, n % page_size] = kr[0, :, 0]
+            v_cache[page, :, n % page_size] = v[r0 + i]
+    if q is None:
+        q_rot = k_cache.new_empty(0)
+    else:
+        q_rot = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        for b, (r0, r1) in enumerate(_clamped_ranges(cu_seqlens_q, q.size(0))):
+            if r1 == r0:
+                continue
+            pos = torch.tensor([min(max(new_lens[b] - (r1 - r0) + i, 0), max_pos - 1) for i in range(r1 - r0)],
+                               dtype=torch.int64, device=q.device)
+            q_rot[r0:r1] = _rope_reference(q[r0:r1].transpose(0, 1)[None], cos[pos], sin[pos])[0].transpose(0, 1)
+    return torch.tensor(new_lens, dtype=torch.int32, device=cache_seqlens.device), q_rot
+
+
+@torch.library.register_kernel("flash_attention::kvcache_append_varlen", "cuda")
+def flash_attention_kvcache_append_varlen_cuda(k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor,
+                                               v: torch.Tensor, cu_seqlens_new: torch.Tensor,
+                                               cache_seqlens: torch.Tensor, block_table: torch.Tensor,
+                                               rotary_cos: Optional[torch.Tensor] = None,
+                                               rotary_sin: Optional[torch.Tensor] = None,
+                                               q: Optional[torch.Tensor] = None,
+                                               cu_seqlens_q: Optional[torch.Tensor] = None
+                                               ) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    if k_cache.dtype == FP8_DTYPE:
+        raise NotImplementedError("flash_attn_kvcache_append_varlen writes 16-bit paged caches only: use "
+                                  "flash_attn_kvcache_append per chunk length for an FP8 cache")
+    # the inputs may be copied to make their last dimension contiguous; the caches never are
+    k, v, q = (t.contiguous() if t is not None and t.stride(-1) != 1 else t for t in (k, v, q))
+    if rotary_cos is not None:
+        rotary_cos, rotary_sin = rotary_cos.to(k_cache.dtype), rotary_sin.to(k_cache.dtype)
+    new_seqlens, q_rot = flash_attention_cuda.flash_attention_kvcache_append_varlen(
+        k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table, rotary_cos, rotary_sin, q, cu_seqlens_q)
+    return new_seqlens, q_rot
+
+
+@torch.library.register_fake("flash_attention::kvcache_append_varlen")
+def flash_attention_kvcache_append_varlen_fake(k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table,
+                                               rotary_cos=None, rotary_sin=None, q=None, cu_seqlens_q=None):
+    q_rot = k_cache.new_empty(0) if q is None else torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format), q_rot
+
+
+def flash_attn_kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table,
+                                     rotary_cos=None, rotary_sin=None, q=None, cu_seqlens_q=None):
+    """Append RAGGED new keys / values to a paged KV cache IN PLACE, one HIP launch: ``k`` / ``v`` [total_new,
+    Hkv, D] packed, sequence b owning rows ``[cu_seqlens_new[b], cu_seqlens_new[b + 1])`` (int32 [B + 1]). Token
+    i of sequence b is written at position ``n = cache_seqlens[b] + i`` -- row ``n % page_size`` of page
+    ``block_table[b, n // page_size]`` -- under ``flash_attn_kvcache_append``'s rules to the letter: with the
+    rotary tables [max_pos, D] k is rotated at ``min(n, max_pos - 1)``, bit for bit as ``apply_rope`` would; a
+    write is DROPPED, never redirected, past the capacity ``max_pages * page_size`` or on a page id outside
+    ``[0, num_pages)``; only the written cache rows are touched. Returns ``new_seqlens`` (int32 [B]:
+    ``min(len_b + n_b, capacity)``; ``cache_seqlens`` is not modified), or ``(new_seqlens, q_rotated)`` when ``q``
+    [total_q, Hq, D] is given with its own ``cu_seqlens_q``: row i of sequence b's ``Sq_b`` rows rotated at
+    ``max(new_seqlens[b] - Sq_b + i, 0)`` -- the sequence's last ``Sq_b`` positions after the append, the
+    convention of ``flash_attn_paged_varlen_func``.
+
+    Both cumulative arrays are clamped on the device (a start into ``[0, total]``, an end into ``[start,
+    total]``), so a bad array never reads outside the inputs. 16-bit paged caches only (dense caches and the FP8
+    quantizing append: ``flash_attn_kvcache_append`` per chunk length). No host synchronisation."""
+    new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append_varlen(
+        k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table, rotary_cos, rotary_sin, q, cu_seqlens_q)
+    return new_seqlens if q is None else (new_seqlens, q_rot)
+
+
+def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, k=None, v=None,
+                                   cu_seqlens_new=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
+                                   block_table=None, softmax_scale=None, causal=False, window_left=-1,
+                                   return_seqlens=False):
+    """One step of a continuous batch on the paged cache, ``flash_attn_with_kvcache`` in the packed layout: the
+    new ``k`` / ``v`` [total_new, Hkv, D] are appended in place at ``cache_seqlens``
+    (``flash_attn_kvcache_append_varlen``; ``cu_seqlens_new`` defaults to ``cu_seqlens_q``, a step's new tokens
+    being its queries), with the rotary tables k is rotated at its new positions and ``q`` [total_q, Hq, D] at
+    each sequence's last ``Sq_b`` positions after the append, then q attends over the advanced lengths
+    (``flash_attn_paged_varlen_func``, whose contract applies). Returns ``out`` [total_q, Hq, D], or ``(out,
+    new_seqlens)`` with ``return_seqlens=True``; ``cache_seqlens`` is not modified. Two launches and no host
+    synchronisation, so the step can be captured in a graph."""
+    if cache_seqlens is None or block_table is None:
+        raise ValueError("flash_attn_varlen_with_kvcache needs cache_seqlens (int32 [batch]) and block_table")
+    if (k is None) != (v is None):
+        raise ValueError("k and v must be given together")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("rotary_cos and rotary_sin must be given together")
+    softmax_scale = _default_scale(q, softmax_scale)
+    new_seqlens, q_rot = cache_seqlens, q
+    if k is not None or rotary_cos is not None:
+        if k is None:  # (q rotated at the current lengths: an append of no token)
+            k = v = q.new_empty((0, k_cache.size(1), q.size(-1)))
+            cu_seqlens_new = torch.zeros_like(cu_seqlens_q)
+        elif cu_seqlens_new is None:
+            cu_seqlens_new = cu_seqlens_q
+        if rotary_cos is not None:  # (cast as apply_rope casts its tables)
+            new_seqlens, q_rot = torch.ops.flash_attention.kvcache_append_varlen(
+                k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table, rotary_cos.to(q.dtype),
+                rotary_sin.to(q.dtype), q, cu_seqlens_q)
+        else:
+            new_seqlens, _ = torch.ops.flash_attention.kvcache_append_varlen(
+                k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table)
+    out = flash_attn_paged_varlen_func(q_rot, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, new_seqlens,
+                                       softmax_scale, causal, window_left)
+    return (out, new_seqlens) if return_seqlens else out
