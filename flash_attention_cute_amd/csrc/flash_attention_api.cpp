@@ -11,8 +11,9 @@
 //   * inputs whose base pointer or strides are not 16-byte aligned (the reference silently assumes
 //     alignment, csrc/flash_attention_template.cuh:135-137) are copied to a contiguous buffer.
 //
-// Every entry point reads: its checks, its layout decisions, one fill_params call, the fields where its
-// layout deviates from the dense 4-D one, its call. The steps they share are named once, below.
+// Every entry point reads: its checks, its layout decisions, one fill_params call (fill_packed_params for packed
+// rows; fill_paged behind either for a paged cache), the fields where its layout deviates, its call
+// (launch_with_workspace where the launch takes scratch). The steps they share are named once, below.
 #include <torch/extension.h>
 
 #include <c10/core/DeviceGuard.h>
@@ -207,6 +208,248 @@ fa_rope_params rope_params(const torch::Tensor &x, const torch::Tensor &out, con
     return r;
 }
 
+// The packed 3-D problem of q / o [total_q, Hq, D] and k / v [total_k, Hkv, D] over `batch` sequences, not
+// fill_params' dense one: rows are dimension 0, the strides are taken as they are, and the four batch strides stay
+// as the caller zeroed them (a sequence starts at row cu_seqlens[b]).
+bool aligned_rows(const torch::Tensor &t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && (t.stride(0) % 8 == 0 || t.size(0) <= 1) &&
+           (t.stride(1) % 8 == 0 || t.size(1) <= 1);
+}
+void fill_packed_params(fa_fwd_params &params, const torch::Tensor &qx, const torch::Tensor &kx, const torch::Tensor &vx,
+                        const torch::Tensor &o, int64_t batch, int64_t max_seqlen_q, int64_t max_seqlen_k,
+                        float softmax_scale) {
+    params.q_ptr = qx.data_ptr();
+    params.k_ptr = kx.data_ptr();
+    params.v_ptr = vx.data_ptr();
+    params.o_ptr = o.data_ptr();
+    params.batch_size = batch;
+    params.num_heads_q = qx.size(1);
+    params.num_heads_kv = kx.size(1);
+    params.seqlen_q = max_seqlen_q;
+    params.seqlen_kv = max_seqlen_k;
+    params.headdim = qx.size(2);
+    params.head_q_per_group = qx.size(1) / kx.size(1);
+    params.q_head_stride = qx.stride(1);
+    params.k_head_stride = kx.stride(1);
+    params.v_head_stride = vx.stride(1);
+    params.o_head_stride = o.stride(1);
+    params.q_seqlen_stride = qx.stride(0);
+    params.k_seqlen_stride = kx.stride(0);
+    params.v_seqlen_stride = vx.stride(0);
+    params.o_seqlen_stride = o.stride(0);
+    softmax_scale *= M_LOG2E;  // (as fill_params)
+    params.softmax_scale = softmax_scale;
+}
+
+// The steps of every entry whose launch takes fp32 scratch: the size query (negative: the library's own
+// message), the scratch, the launch. `name` is the C entry (its size query: <name>_workspace_size).
+template <class SizeFn, class LaunchFn>
+void launch_with_workspace(const char *name, SizeFn size_fn, LaunchFn launch_fn, const torch::TensorOptions &options,
+                           const char *launch_name = nullptr) {
+    const int64_t ws_bytes = size_fn();
+    TORCH_CHECK(ws_bytes >= 0, name, "_workspace_size failed: ", fa_last_error());
+    torch::Tensor ws = workspace_for(ws_bytes, options);
+    check_rc(launch_fn(data_or_null(ws), ws_bytes), launch_name ? launch_name : name);
+}
+
+// A paged KV cache as an attention entry sees it: the pools [num_pages, Hkv, page_size, D], block_table int32
+// [batch, max_pages] and cache_seqlens int32 [batch]. The entries differ in three ways, each on purpose:
+struct PagedCacheOptions {
+    int page_multiple;        // 32: the decode kernels' key tile; 64: the paged fa_fwd_w4's
+    bool copy_table;          // a table whose column stride is not 1: copied, or refused (read in place, to the letter)
+    bool lengths_required;    // false: without cache_seqlens every sequence has seqlen_offset keys
+    bool one_device_message;  // the wording only: "block_table and cache_seqlens must be on the device of q" in one
+                              // check behind both shape checks, or one message each
+};
+// (page_multiple, copy_table, lengths_required, one_device_message)
+constexpr PagedCacheOptions kPagedDecode = {32, true, true, true};    // the entries of paged_fwd_impl
+constexpr PagedCacheOptions kPagedLse = {32, false, false, false};    // flash_attention_paged_lse_fwd
+constexpr PagedCacheOptions kPagedRagged = {64, false, true, false};  // flash_attention_paged_varlen_fwd
+
+// The tensors behind the raw pointers of a fa_paged_params: they stay alive as long as this struct.
+struct PagedCache {
+    torch::Tensor k, v, table, seqlens;  // (seqlens undefined: none given)
+};
+
+// The pools' own shape rules, in two pieces like the dense checks: these are reachable with CPU tensors (every
+// paged entry calls check_headdim_device behind them), paged_cache's are not.
+void check_pools(const torch::Tensor &k_cache, const torch::Tensor &v_cache, const PagedCacheOptions &opts) {
+    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4, "the caches must be 4-D [pages, heads, page_size, dim]");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
+    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % opts.page_multiple == 0,
+                "page_size must be a positive multiple of ", opts.page_multiple);
+}
+
+void check_table(const torch::Tensor &block_table, int64_t batch) {
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == batch &&
+                    block_table.size(1) > 0,
+                "block_table must be int32 [batch, max_pages]");
+}
+// (the appends and the unwindowed decode copy; a [batch, 1] table is copied too, as it always was)
+torch::Tensor table_with_contiguous_rows(const torch::Tensor &t) { return t.stride(1) == 1 ? t : t.contiguous(); }
+
+// The table and the lengths of `batch` sequences on q's device, checked; the table copied where the entry allows it.
+PagedCache paged_cache(const torch::Tensor &k_cache, const torch::Tensor &v_cache, const torch::Tensor &block_table,
+                       const c10::optional<torch::Tensor> &cache_seqlens, int64_t batch, const torch::Device &device,
+                       const PagedCacheOptions &opts) {
+    TORCH_INTERNAL_ASSERT(cache_seqlens.has_value() || !opts.lengths_required);
+    const bool each = !opts.one_device_message;
+    check_table(block_table, batch);
+    TORCH_CHECK(!each || block_table.device() == device, "block_table must be on the device of q");
+    TORCH_CHECK(opts.copy_table || block_table.stride(1) == 1 || block_table.size(1) == 1,
+                "block_table rows must be contiguous (the table is read in place)");
+    if (cache_seqlens.has_value()) {
+        TORCH_CHECK(cache_seqlens->dtype() == torch::kInt32 && cache_seqlens->dim() == 1 && cache_seqlens->size(0) == batch,
+                    "cache_seqlens must be int32 [batch]");
+        TORCH_CHECK(!each || cache_seqlens->device() == device, "cache_seqlens must be on the device of q");
+    }
+    TORCH_CHECK(each || (block_table.device() == device && (!cache_seqlens.has_value() || cache_seqlens->device() == device)),
+                "block_table and cache_seqlens must be on the device of q");
+    return PagedCache{k_cache, v_cache, opts.copy_table ? table_with_contiguous_rows(block_table) : block_table,
+                      cache_seqlens.has_value() ? *cache_seqlens : torch::Tensor()};
+}
+
+// Every field of `pp` that depends on the cache, over a base that fill_params / fill_packed_params filled for the
+// pools as given. The pool is read where it is; only a 16-bit pool whose strides are not 16-byte multiples is copied
+// (an fp8 pool never: the library rejects one that is not 16-byte aligned). The copies, the lengths' included, are
+// made here and not in paged_cache: an entry that returns early with nothing to launch has copied nothing.
+void fill_paged(fa_paged_params &pp, PagedCache &c) {
+    if (c.k.dtype() != at::kFloat8_e4m3fn) {
+        c.k = aligned_or_contiguous(c.k);
+        c.v = aligned_or_contiguous(c.v);
+    }
+    if (c.seqlens.defined()) c.seqlens = c.seqlens.contiguous();
+    fa_fwd_params &params = pp.base;
+    params.k_ptr = c.k.data_ptr();
+    params.v_ptr = c.v.data_ptr();
+    params.seqlen_kv = c.table.size(1) * c.k.size(2);
+    params.k_batch_stride = stride_or_zero(c.k, 0);  // (the page stride)
+    params.v_batch_stride = stride_or_zero(c.v, 0);
+    params.k_head_stride = stride_or_zero(c.k, 1);
+    params.v_head_stride = stride_or_zero(c.v, 1);
+    params.k_seqlen_stride = c.k.stride(2);
+    params.v_seqlen_stride = c.v.stride(2);
+    pp.block_table = c.table.data_ptr<int32_t>();
+    pp.block_table_stride = c.table.stride(0);
+    pp.max_pages = c.table.size(1);
+    pp.num_pages = c.k.size(0);
+    pp.page_size = c.k.size(2);
+    pp.seqlens_k = c.seqlens.defined() ? c.seqlens.data_ptr<int32_t>() : nullptr;
+}
+
+// q [B, Hq, Sq, D] against the pools: the checks the 4-D paged entries share, up to their data types
+void check_q_and_pools(const torch::Tensor &q, const torch::Tensor &k_cache, const torch::Tensor &v_cache,
+                       const PagedCacheOptions &opts) {
+    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
+                "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
+    check_pools(k_cache, v_cache, opts);
+    TORCH_CHECK(q.size(3) == k_cache.size(3), "q and the caches must have the same hidden dimension");
+    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0, "q must have at least one element");
+    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
+                "number of heads in q must be multiple of number of heads in k and v");
+}
+
+// The [B, Hkv] fp32 descales of an fp8 entry (nullptr / undefined tensor: 1.0)
+struct Fp8Descales {
+    const torch::Tensor *k, *v;
+};
+Fp8Descales descales_of(const c10::optional<torch::Tensor> &k, const c10::optional<torch::Tensor> &v) {
+    return Fp8Descales{k.has_value() ? &*k : nullptr, v.has_value() ? &*v : nullptr};
+}
+
+// their pointers and the strides both share, into either fp8 struct; returns the tensors behind the pointers
+template <class Fp8Params>
+std::pair<torch::Tensor, torch::Tensor> fill_descales(Fp8Params &fp, const Fp8Descales &ds, const torch::Tensor &like,
+                                                      int64_t bs, int64_t hkv) {
+    auto prep = [&](const torch::Tensor *t, const char *name) {
+        if (!t || !t->defined()) return torch::Tensor();
+        TORCH_CHECK(t->dtype() == torch::kFloat32 && t->dim() == 2 && t->size(0) == bs && t->size(1) == hkv, name,
+                    " must be fp32 [batch, kv heads]");
+        TORCH_CHECK(t->device() == like.device(), name, " must be on the device of q / the caches");
+        return *t;
+    };
+    torch::Tensor keep_k = prep(ds.k, "k_descale"), keep_v = prep(ds.v, "v_descale");
+    // one stride pair serves both arrays: a tensor laid out differently from the other is made contiguous
+    if (keep_k.defined() && keep_v.defined() &&
+        (stride_or_zero(keep_k, 0) != stride_or_zero(keep_v, 0) || stride_or_zero(keep_k, 1) != stride_or_zero(keep_v, 1) ||
+         keep_k.stride(0) < 0 || keep_k.stride(1) < 0)) {
+        keep_k = keep_k.contiguous();
+        keep_v = keep_v.contiguous();
+    }
+    const torch::Tensor &any = keep_k.defined() ? keep_k : keep_v;
+    fp.k_descale = keep_k.defined() ? keep_k.data_ptr<float>() : nullptr;
+    fp.v_descale = keep_v.defined() ? keep_v.data_ptr<float>() : nullptr;
+    fp.descale_batch_stride = any.defined() ? stride_or_zero(any, 0) : 0;
+    fp.descale_head_stride = any.defined() ? stride_or_zero(any, 1) : 0;
+    return {keep_k, keep_v};
+}
+
+// the LSE destination of either LSE struct
+template <class LseParams>
+void fill_lse(LseParams &lp, const torch::Tensor &lse, int64_t seqlen_offset) {
+    lp.lse_ptr = lse.data_ptr<float>();
+    lp.lse_batch_stride = lse.stride(0);
+    lp.lse_head_stride = lse.stride(1);
+    lp.lse_seqlen_stride = lse.stride(2);
+    lp.seqlen_offset = seqlen_offset;
+}
+
+// The [max_pos, D] cos / sin tables of an append, of `dtype` on the caches' device (`dtype_words`: how the entry
+// names that dtype), with contiguous rows and one row stride; both undefined when none are given.
+std::pair<torch::Tensor, torch::Tensor> append_rope_tables(const c10::optional<torch::Tensor> &cos,
+                                                           const c10::optional<torch::Tensor> &sin, int64_t d,
+                                                           caffe2::TypeMeta dtype, const torch::Device &device,
+                                                           const char *dtype_words) {
+    if (!cos.has_value()) return {};
+    TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
+    auto table = [&](const torch::Tensor &t, const char *name) {
+        TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
+        TORCH_CHECK(t.dtype() == dtype, name, dtype_words);
+        TORCH_CHECK(t.device() == device, name, " must be on the device of the caches");
+        return t.stride(1) == 1 ? t : t.contiguous();
+    };
+    torch::Tensor cs = table(*cos, "rotary_cos"), sn = table(*sin, "rotary_sin");
+    TORCH_CHECK(cs.size(0) == sn.size(0), "rotary_cos and rotary_sin must have the same number of rows");
+    if (cs.size(0) > 1 && cs.stride(0) != sn.stride(0)) {
+        cs = cs.contiguous();
+        sn = sn.contiguous();
+    }
+    return {cs, sn};
+}
+
+// The fields either append struct names alike: the tables, the cache the rows go to (`bt` undefined: a dense
+// [B, Hkv, Smax, D] cache, one "page" per batch row) and the lengths in and out.
+template <class AppendParams>
+void fill_append_cache(AppendParams &p, const torch::Tensor &k_cache, const torch::Tensor &v_cache,
+                       const torch::Tensor &bt, const torch::Tensor &sl, const torch::Tensor &new_seqlens,
+                       const torch::Tensor &cs, const torch::Tensor &sn) {
+    if (cs.defined()) {
+        p.cos = cs.data_ptr();
+        p.sin = sn.data_ptr();
+        p.cs_row_stride = stride_or_zero(cs, 0);
+        p.max_pos = cs.size(0);
+    }
+    p.k_cache = k_cache.data_ptr();
+    p.v_cache = v_cache.data_ptr();
+    p.k_page_stride = stride_or_zero(k_cache, 0);
+    p.k_head_stride = stride_or_zero(k_cache, 1);
+    p.k_row_stride = stride_or_zero(k_cache, 2);
+    p.v_page_stride = stride_or_zero(v_cache, 0);
+    p.v_head_stride = stride_or_zero(v_cache, 1);
+    p.v_row_stride = stride_or_zero(v_cache, 2);
+    p.block_table = bt.defined() ? bt.data_ptr<int32_t>() : nullptr;
+    p.block_table_stride = bt.defined() ? bt.stride(0) : 0;
+    p.max_pages = bt.defined() ? bt.size(1) : 1;
+    p.num_pages = k_cache.size(0);
+    p.page_size = k_cache.size(2);
+    p.seqlens_k = sl.data_ptr<int32_t>();
+    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
+    p.batch_size = sl.size(0);
+    p.num_heads_kv = k_cache.size(1);
+    p.headdim = k_cache.size(3);
+}
+
 }  // namespace
 
 // out = x * cos + rotate_half(x) * sin for x [B, H, S, D] (fp16 / bf16, last dim contiguous); out keeps
@@ -266,17 +509,17 @@ torch::Tensor fwd_impl(torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, flo
     fa_fwd_params params;
     fill_params(params, qx, kx, vx, o, softmax_scale);
 
-    const int dtype = fa_dtype(qx);
+    const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
     void *stream = current_stream(qx);
     if (window_left >= 0) {
-        check_rc(fa_fwd_gfx950_window(&params, dtype, causal ? 1 : 0, window_left, stream), "fa_fwd_gfx950_window");
+        check_rc(fa_fwd_gfx950_window(&params, dtype, c, window_left, stream), "fa_fwd_gfx950_window");
         return shaped_like(o, q);
     }
     // split-KV decode (few rows per kv-head) and key-split causal blocks want fp32 scratch for their partials
-    const int64_t ws_bytes = fa_fwd_gfx950_workspace_size(&params, dtype, causal ? 1 : 0);
-    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-    check_rc(fa_fwd_gfx950_ws(&params, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, stream), "fa_fwd_gfx950_ws");
+    launch_with_workspace(
+        "fa_fwd_gfx950", [&] { return fa_fwd_gfx950_workspace_size(&params, dtype, c); },
+        [&](void *ws, int64_t ws_bytes) { return fa_fwd_gfx950_ws(&params, dtype, c, ws, ws_bytes, stream); },
+        qx.options(), "fa_fwd_gfx950_ws");
     return shaped_like(o, q);
 }
 
@@ -377,41 +620,14 @@ torch::Tensor flash_attention_varlen_fwd(torch::Tensor &q, torch::Tensor &k, tor
     if (q.size(0) == 0 || max_seqlen_q == 0) return o;
     if (max_seqlen_k == 0) return o.zero_();  // no sequence has a key: every row is 0
 
-    auto aligned_rows = [](const torch::Tensor &t) {
-        return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && (t.stride(0) % 8 == 0 || t.size(0) <= 1) &&
-               (t.stride(1) % 8 == 0 || t.size(1) <= 1);
-    };
     torch::Tensor qx = aligned_rows(q) ? q : q.contiguous();
     torch::Tensor kx = aligned_rows(k) ? k : k.contiguous();
     torch::Tensor vx = aligned_rows(v) ? v : v.contiguous();
     if (!aligned_rows(o)) o = torch::empty(q.sizes(), q.options());
     torch::Tensor cq = cu_seqlens_q.contiguous(), ck = cu_seqlens_k.contiguous();
 
-    // the packed 3-D layout, not fill_params' dense one: rows are dimension 0, the strides are taken as
-    // they are, and the four batch strides stay 0 (a sequence starts at row cu_seqlens[b])
     fa_varlen_params vp = {};
-    fa_fwd_params &params = vp.base;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = cq.size(0) - 1;
-    params.num_heads_q = qx.size(1);
-    params.num_heads_kv = kx.size(1);
-    params.seqlen_q = max_seqlen_q;
-    params.seqlen_kv = max_seqlen_k;
-    params.headdim = qx.size(2);
-    params.head_q_per_group = qx.size(1) / kx.size(1);
-    params.q_head_stride = qx.stride(1);
-    params.k_head_stride = kx.stride(1);
-    params.v_head_stride = vx.stride(1);
-    params.o_head_stride = o.stride(1);
-    params.q_seqlen_stride = qx.stride(0);
-    params.k_seqlen_stride = kx.stride(0);
-    params.v_seqlen_stride = vx.stride(0);
-    params.o_seqlen_stride = o.stride(0);
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
+    fill_packed_params(vp.base, qx, kx, vx, o, cq.size(0) - 1, max_seqlen_q, max_seqlen_k, softmax_scale);
     vp.cu_seqlens_q = cq.data_ptr<int32_t>();
     vp.cu_seqlens_k = ck.data_ptr<int32_t>();
 
@@ -516,13 +732,13 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
     pp.k_start = ks.data_ptr<int32_t>();
     pp.k_end = ke.data_ptr<int32_t>();
 
-    const int dtype = fa_dtype(qx);
-    const int64_t ws_bytes = fa_fwd_gfx950_padded_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
-    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_padded_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-    check_rc(fa_fwd_gfx950_padded(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
-                                  current_stream(qx)),
-             "fa_fwd_gfx950_padded");
+    const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    launch_with_workspace(
+        "fa_fwd_gfx950_padded", [&] { return fa_fwd_gfx950_padded_workspace_size(&pp, dtype, c, window_left); },
+        [&](void *ws, int64_t ws_bytes) {
+            return fa_fwd_gfx950_padded(&pp, dtype, c, window_left, ws, ws_bytes, current_stream(qx));
+        },
+        qx.options());
     return shaped_like(o, q);
 }
 
@@ -542,49 +758,10 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // goes to the windowed entries WITHOUT the q-head pack -- the window is relative to the real Sq, so a decode
 // step is passed as Sq 1 with g q-heads per kv-head (the same kernel rows and arithmetic as the pack, causal
 // dropped as the pack drops it); window_left < 0 is the unwindowed call, to the letter.
-struct Fp8Descales {
-    const torch::Tensor *k, *v;  // nullptr / undefined tensor: 1.0
-};
-
-// the [B, Hkv] fp32 descales of an fp8 entry: pointers and the strides both share
-void fill_descales(const Fp8Descales &ds, const torch::Tensor &like, int64_t bs, int64_t hkv, const float *&kd,
-                   const float *&vd, int64_t &batch_stride, int64_t &head_stride, torch::Tensor &keep_k,
-                   torch::Tensor &keep_v) {
-    auto prep = [&](const torch::Tensor *t, const char *name) {
-        if (!t || !t->defined()) return torch::Tensor();
-        TORCH_CHECK(t->dtype() == torch::kFloat32 && t->dim() == 2 && t->size(0) == bs && t->size(1) == hkv, name,
-                    " must be fp32 [batch, kv heads]");
-        TORCH_CHECK(t->device() == like.device(), name, " must be on the device of q / the caches");
-        return *t;
-    };
-    keep_k = prep(ds.k, "k_descale");
-    keep_v = prep(ds.v, "v_descale");
-    // one stride pair serves both arrays: a tensor laid out differently from the other is made contiguous
-    if (keep_k.defined() && keep_v.defined() &&
-        (stride_or_zero(keep_k, 0) != stride_or_zero(keep_v, 0) || stride_or_zero(keep_k, 1) != stride_or_zero(keep_v, 1) ||
-         keep_k.stride(0) < 0 || keep_k.stride(1) < 0)) {
-        keep_k = keep_k.contiguous();
-        keep_v = keep_v.contiguous();
-    }
-    const torch::Tensor &any = keep_k.defined() ? keep_k : keep_v;
-    kd = keep_k.defined() ? keep_k.data_ptr<float>() : nullptr;
-    vd = keep_v.defined() ? keep_v.data_ptr<float>() : nullptr;
-    batch_stride = any.defined() ? stride_or_zero(any, 0) : 0;
-    head_stride = any.defined() ? stride_or_zero(any, 1) : 0;
-}
-
 torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
                              torch::Tensor &block_table, torch::Tensor &cache_seqlens, float softmax_scale,
                              bool causal, const Fp8Descales *fp8, int64_t window_left = -1, bool prefill = false) {
-    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
-                "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
-    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
-    TORCH_CHECK(q.size(3) == k_cache.size(3), "q and the caches must have the same hidden dimension");
-    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0, "q must have at least one element");
-    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
-    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
-                "number of heads in q must be multiple of number of heads in k and v");
-    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
+    check_q_and_pools(q, k_cache, v_cache, kPagedDecode);
     if (fp8) {
         TORCH_CHECK(k_cache.dtype() == at::kFloat8_e4m3fn && v_cache.dtype() == at::kFloat8_e4m3fn,
                     "the fp8 caches must be torch.float8_e4m3fn");
@@ -595,27 +772,14 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     TORCH_CHECK(q.stride(3) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
                 "q, k, v must be contiguous in the last dimension");
     check_headdim_device(q, k_cache, v_cache);
-    const int64_t bs = q.size(0);
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
-                    block_table.size(1) > 0,
-                "block_table must be int32 [batch, max_pages]");
-    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
-                "cache_seqlens must be int32 [batch]");
-    TORCH_CHECK(block_table.device() == q.device() && cache_seqlens.device() == q.device(),
-                "block_table and cache_seqlens must be on the device of q");
+    PagedCache cache = paged_cache(k_cache, v_cache, block_table, cache_seqlens, q.size(0), q.device(), kPagedDecode);
     c10::DeviceGuard device_guard(q.device());
     require_gfx950(q.device());
 
-    // the pool is read where it is; only a 16-bit pool whose strides are not 16-byte multiples is copied
-    // (an fp8 pool never: the library rejects one that is not 16-byte aligned)
     torch::Tensor qx = aligned_or_contiguous(q);
-    torch::Tensor kx = fp8 ? k_cache : aligned_or_contiguous(k_cache);
-    torch::Tensor vx = fp8 ? v_cache : aligned_or_contiguous(v_cache);
-    torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
-    torch::Tensor sl = cache_seqlens.contiguous();
     const bool window = window_left >= 0;
     if (qx.size(2) == 1 && !prefill) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
-        if (!window) qx = pack_head_q(qx, kx.size(1));
+        if (!window) qx = pack_head_q(qx, k_cache.size(1));
         causal = false;
     }
     auto o = alloc_out_like(qx);
@@ -623,63 +787,41 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     fa_paged_fp8_params fp;
     memset(&fp, 0, sizeof(fp));
     fa_paged_params &pp = fp.paged;
-    fa_fwd_params &params = pp.base;
-    fill_params(params, qx, kx, vx, o, softmax_scale);  // (k / v batch stride: the page stride)
-    params.seqlen_kv = bt.size(1) * kx.size(2);
-    params.k_seqlen_stride = kx.stride(2);
-    params.v_seqlen_stride = vx.stride(2);
-    pp.block_table = bt.data_ptr<int32_t>();
-    pp.block_table_stride = bt.stride(0);
-    pp.max_pages = bt.size(1);
-    pp.num_pages = kx.size(0);
-    pp.page_size = kx.size(2);
-    pp.seqlens_k = sl.data_ptr<int32_t>();
+    fill_params(pp.base, qx, k_cache, v_cache, o, softmax_scale);
+    fill_paged(pp, cache);
+    // (prefill: 16-bit pools only, the Python op keeps FP8 pools on its copying path)
+    TORCH_CHECK(!prefill || !fp8, "the paged prefill kernel reads 16-bit pools only");
+    std::pair<torch::Tensor, torch::Tensor> descales;
+    if (fp8) descales = fill_descales(fp, *fp8, q, q.size(0), k_cache.size(1));
 
-    const int dtype = fa_dtype(qx);
-    if (prefill) {  // (16-bit pools only: the Python op keeps FP8 pools on its copying path)
-        TORCH_CHECK(!fp8, "the paged prefill kernel reads 16-bit pools only");
-        const int64_t ws_bytes = fa_fwd_gfx950_paged_prefill_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
-        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_prefill_workspace_size failed: ", fa_last_error());
-        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-        check_rc(fa_fwd_gfx950_paged_prefill(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
-                                             current_stream(qx)),
-                 "fa_fwd_gfx950_paged_prefill");
-        return shaped_like(o, q);
-    }
-    if (fp8) {
-        torch::Tensor keep_k, keep_v;
-        fill_descales(*fp8, q, bs, kx.size(1), fp.k_descale, fp.v_descale, fp.descale_batch_stride,
-                      fp.descale_head_stride, keep_k, keep_v);
-        if (window) {
-            const int64_t ws_bytes = fa_fwd_gfx950_paged_window_fp8_workspace_size(&fp, dtype, causal ? 1 : 0, window_left);
-            TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_window_fp8_workspace_size failed: ", fa_last_error());
-            torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-            check_rc(fa_fwd_gfx950_paged_window_fp8(&fp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
-                                                    current_stream(qx)),
-                     "fa_fwd_gfx950_paged_window_fp8");
-            return shaped_like(o, q);
-        }
-        const int64_t ws_bytes = fa_fwd_gfx950_paged_fp8_workspace_size(&fp, dtype, causal ? 1 : 0);
-        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_fp8_workspace_size failed: ", fa_last_error());
-        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-        check_rc(fa_fwd_gfx950_paged_fp8(&fp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
-                 "fa_fwd_gfx950_paged_fp8");
-        return shaped_like(o, q);
-    }
-    if (window) {
-        const int64_t ws_bytes = fa_fwd_gfx950_paged_window_workspace_size(&pp, dtype, causal ? 1 : 0, window_left);
-        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_window_workspace_size failed: ", fa_last_error());
-        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-        check_rc(fa_fwd_gfx950_paged_window(&pp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
-                                            current_stream(qx)),
-                 "fa_fwd_gfx950_paged_window");
-        return shaped_like(o, q);
-    }
-    const int64_t ws_bytes = fa_fwd_gfx950_paged_workspace_size(&pp, dtype, causal ? 1 : 0);
-    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-    check_rc(fa_fwd_gfx950_paged(&pp, dtype, causal ? 1 : 0, data_or_null(ws), ws_bytes, current_stream(qx)),
-             "fa_fwd_gfx950_paged");
+    // one of five C entries, each with the size query of its name
+    enum Entry { kPrefill, kWindowFp8, kFp8, kWindow, kPlain };
+    static const char *const names[] = {"fa_fwd_gfx950_paged_prefill", "fa_fwd_gfx950_paged_window_fp8",
+                                        "fa_fwd_gfx950_paged_fp8", "fa_fwd_gfx950_paged_window", "fa_fwd_gfx950_paged"};
+    const Entry entry = prefill ? kPrefill : fp8 ? (window ? kWindowFp8 : kFp8) : window ? kWindow : kPlain;
+    const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    void *stream = current_stream(qx);
+    launch_with_workspace(
+        names[entry],
+        [&]() -> int64_t {
+            switch (entry) {
+                case kPrefill: return fa_fwd_gfx950_paged_prefill_workspace_size(&pp, dtype, c, window_left);
+                case kWindowFp8: return fa_fwd_gfx950_paged_window_fp8_workspace_size(&fp, dtype, c, window_left);
+                case kFp8: return fa_fwd_gfx950_paged_fp8_workspace_size(&fp, dtype, c);
+                case kWindow: return fa_fwd_gfx950_paged_window_workspace_size(&pp, dtype, c, window_left);
+                default: return fa_fwd_gfx950_paged_workspace_size(&pp, dtype, c);
+            }
+        },
+        [&](void *ws, int64_t ws_bytes) -> int {
+            switch (entry) {
+                case kPrefill: return fa_fwd_gfx950_paged_prefill(&pp, dtype, c, window_left, ws, ws_bytes, stream);
+                case kWindowFp8: return fa_fwd_gfx950_paged_window_fp8(&fp, dtype, c, window_left, ws, ws_bytes, stream);
+                case kFp8: return fa_fwd_gfx950_paged_fp8(&fp, dtype, c, ws, ws_bytes, stream);
+                case kWindow: return fa_fwd_gfx950_paged_window(&pp, dtype, c, window_left, ws, ws_bytes, stream);
+                default: return fa_fwd_gfx950_paged(&pp, dtype, c, ws, ws_bytes, stream);
+            }
+        },
+        qx.options());
     return shaped_like(o, q);
 }
 
@@ -693,7 +835,7 @@ torch::Tensor flash_attention_paged_fp8_fwd(torch::Tensor &q, torch::Tensor &k_c
                                             torch::Tensor &block_table, torch::Tensor &cache_seqlens,
                                             c10::optional<torch::Tensor> k_descale,
                                             c10::optional<torch::Tensor> v_descale, float softmax_scale, bool causal) {
-    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    const Fp8Descales ds = descales_of(k_descale, v_descale);
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds);
 }
 
@@ -718,7 +860,7 @@ torch::Tensor flash_attention_paged_window_fp8_fwd(torch::Tensor &q, torch::Tens
                                                    int64_t window_left, c10::optional<torch::Tensor> k_descale,
                                                    c10::optional<torch::Tensor> v_descale, float softmax_scale,
                                                    bool causal) {
-    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    const Fp8Descales ds = descales_of(k_descale, v_descale);
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds, window_left);
 }
 
@@ -735,15 +877,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_lse_fwd(
     c10::optional<torch::Tensor> cache_seqlens, int64_t seqlen_offset, c10::optional<torch::Tensor> k_descale,
     c10::optional<torch::Tensor> v_descale, float softmax_scale, bool causal, c10::optional<torch::Tensor> out,
     c10::optional<torch::Tensor> lse_out) {
-    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4,
-                "q must be 4-D [batch, heads, seqlen, dim], the caches 4-D [pages, heads, page_size, dim]");
-    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
-    TORCH_CHECK(q.size(3) == k_cache.size(3), "q and the caches must have the same hidden dimension");
-    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0 && q.size(3) > 0, "q must have at least one element");
-    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
-    TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
-                "number of heads in q must be multiple of number of heads in k and v");
-    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
+    check_q_and_pools(q, k_cache, v_cache, kPagedLse);
     const bool fp8 = k_cache.dtype() == at::kFloat8_e4m3fn;
     if (fp8) {
         TORCH_CHECK(v_cache.dtype() == at::kFloat8_e4m3fn, "the fp8 caches must be torch.float8_e4m3fn");
@@ -756,25 +890,11 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_lse_fwd(
                 "q, k, v must be contiguous in the last dimension");
     check_headdim_device(q, k_cache, v_cache);
     const int64_t bs = q.size(0);
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
-                    block_table.size(1) > 0,
-                "block_table must be int32 [batch, max_pages]");
-    TORCH_CHECK(block_table.device() == q.device(), "block_table must be on the device of q");
-    TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) == 1,
-                "block_table rows must be contiguous (the table is read in place)");
-    torch::Tensor sl;
-    if (cache_seqlens.has_value()) {
-        TORCH_CHECK(cache_seqlens->dtype() == torch::kInt32 && cache_seqlens->dim() == 1 && cache_seqlens->size(0) == bs,
-                    "cache_seqlens must be int32 [batch]");
-        TORCH_CHECK(cache_seqlens->device() == q.device(), "cache_seqlens must be on the device of q");
-        sl = cache_seqlens->contiguous();
-    }
+    PagedCache cache = paged_cache(k_cache, v_cache, block_table, cache_seqlens, bs, q.device(), kPagedLse);
     c10::DeviceGuard device_guard(q.device());
     require_gfx950(q.device());
 
     torch::Tensor qx = aligned_or_contiguous(q);
-    torch::Tensor kx = fp8 ? k_cache : aligned_or_contiguous(k_cache);
-    torch::Tensor vx = fp8 ? v_cache : aligned_or_contiguous(v_cache);
     if (qx.size(2) == 1) causal = false;
     torch::Tensor o;
     if (out.has_value()) {
@@ -800,49 +920,26 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_lse_fwd(
     fa_paged_fp8_lse_params lp8;
     memset(&lp8, 0, sizeof(lp8));
     fa_paged_params &pp = lp8.fp8.paged;
-    fa_fwd_params &params = pp.base;
-    fill_params(params, qx, kx, vx, o, softmax_scale);  // (k / v batch stride: the page stride)
-    params.seqlen_kv = block_table.size(1) * kx.size(2);
-    params.k_seqlen_stride = kx.stride(2);
-    params.v_seqlen_stride = vx.stride(2);
-    pp.block_table = block_table.data_ptr<int32_t>();
-    pp.block_table_stride = block_table.stride(0);
-    pp.max_pages = block_table.size(1);
-    pp.num_pages = kx.size(0);
-    pp.page_size = kx.size(2);
-    pp.seqlens_k = sl.defined() ? sl.data_ptr<int32_t>() : nullptr;
-    const int dtype = fa_dtype(qx);
-    const int c = causal ? 1 : 0;
+    fill_params(pp.base, qx, k_cache, v_cache, o, softmax_scale);
+    fill_paged(pp, cache);
+    const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    void *stream = current_stream(qx);
     if (fp8) {
-        const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr,
-                             v_descale.has_value() ? &*v_descale : nullptr};
-        torch::Tensor keep_k, keep_v;
-        fill_descales(ds, q, bs, kx.size(1), lp8.fp8.k_descale, lp8.fp8.v_descale, lp8.fp8.descale_batch_stride,
-                      lp8.fp8.descale_head_stride, keep_k, keep_v);
-        lp8.lse_ptr = lse.data_ptr<float>();
-        lp8.lse_batch_stride = lse.stride(0);
-        lp8.lse_head_stride = lse.stride(1);
-        lp8.lse_seqlen_stride = lse.stride(2);
-        lp8.seqlen_offset = seqlen_offset;
-        const int64_t ws_bytes = fa_fwd_gfx950_paged_lse_fp8_workspace_size(&lp8, dtype, c, -1);
-        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_lse_fp8_workspace_size failed: ", fa_last_error());
-        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-        check_rc(fa_fwd_gfx950_paged_lse_fp8(&lp8, dtype, c, -1, data_or_null(ws), ws_bytes, current_stream(qx)),
-                 "fa_fwd_gfx950_paged_lse_fp8");
+        const auto descales = fill_descales(lp8.fp8, descales_of(k_descale, v_descale), q, bs, k_cache.size(1));
+        fill_lse(lp8, lse, seqlen_offset);
+        launch_with_workspace(
+            "fa_fwd_gfx950_paged_lse_fp8", [&] { return fa_fwd_gfx950_paged_lse_fp8_workspace_size(&lp8, dtype, c, -1); },
+            [&](void *ws, int64_t ws_bytes) { return fa_fwd_gfx950_paged_lse_fp8(&lp8, dtype, c, -1, ws, ws_bytes, stream); },
+            qx.options());
     } else {
         fa_paged_lse_params lp;
         memset(&lp, 0, sizeof(lp));
         lp.paged = pp;
-        lp.lse_ptr = lse.data_ptr<float>();
-        lp.lse_batch_stride = lse.stride(0);
-        lp.lse_head_stride = lse.stride(1);
-        lp.lse_seqlen_stride = lse.stride(2);
-        lp.seqlen_offset = seqlen_offset;
-        const int64_t ws_bytes = fa_fwd_gfx950_paged_lse_workspace_size(&lp, dtype, c, -1);
-        TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_lse_workspace_size failed: ", fa_last_error());
-        torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-        check_rc(fa_fwd_gfx950_paged_lse(&lp, dtype, c, -1, data_or_null(ws), ws_bytes, current_stream(qx)),
-                 "fa_fwd_gfx950_paged_lse");
+        fill_lse(lp, lse, seqlen_offset);
+        launch_with_workspace(
+            "fa_fwd_gfx950_paged_lse", [&] { return fa_fwd_gfx950_paged_lse_workspace_size(&lp, dtype, c, -1); },
+            [&](void *ws, int64_t ws_bytes) { return fa_fwd_gfx950_paged_lse(&lp, dtype, c, -1, ws, ws_bytes, stream); },
+            qx.options());
     }
     return {o, lse};
 }
@@ -948,9 +1045,7 @@ std::tuple<torch::Tensor, torch::Tensor> kvcache_append_impl(
     TORCH_CHECK(cache_seqlens.device() == k_cache.device(), "cache_seqlens must be on the device of the caches");
     const bool paged = block_table.has_value();
     if (paged) {
-        TORCH_CHECK(block_table->dtype() == torch::kInt32 && block_table->dim() == 2 && block_table->size(0) == bs &&
-                        block_table->size(1) > 0,
-                    "block_table must be int32 [batch, max_pages]");
+        check_table(*block_table, bs);
         TORCH_CHECK(block_table->device() == k_cache.device(), "block_table must be on the device of the caches");
         TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(2) % 32 == 0, "page_size must be a positive multiple of 32");
     } else {
@@ -977,22 +1072,8 @@ std::tuple<torch::Tensor, torch::Tensor> kvcache_append_impl(
         sq = q->size(2);
     }
     torch::Tensor cs, sn_t;
-    if (rotary_cos.has_value()) {
-        TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
-        auto table = [&](const torch::Tensor &t, const char *name) {
-            TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
-            TORCH_CHECK(t.dtype() == io_dtype, name, fp8 ? " must have the data type of k" : " must have the caches' data type");
-            TORCH_CHECK(t.device() == k_cache.device(), name, " must be on the device of the caches");
-            return t.stride(1) == 1 ? t : t.contiguous();
-        };
-        cs = table(*rotary_cos, "rotary_cos");
-        sn_t = table(*rotary_sin, "rotary_sin");
-        TORCH_CHECK(cs.size(0) == sn_t.size(0), "rotary_cos and rotary_sin must have the same number of rows");
-        if (cs.size(0) > 1 && cs.stride(0) != sn_t.stride(0)) {
-            cs = cs.contiguous();
-            sn_t = sn_t.contiguous();
-        }
-    }
+    std::tie(cs, sn_t) = append_rope_tables(rotary_cos, rotary_sin, d, io_dtype, k_cache.device(),
+                                            fp8 ? " must have the data type of k" : " must have the caches' data type");
     c10::DeviceGuard device_guard(k_cache.device());
     require_gfx950(k_cache.device());
 
@@ -1003,8 +1084,8 @@ std::tuple<torch::Tensor, torch::Tensor> kvcache_append_impl(
         return {cache_seqlens.clamp(0, max_pages * page_size), q_rot};
     torch::Tensor sl = cache_seqlens.contiguous();
     torch::Tensor new_seqlens = torch::empty({bs}, sl.options());
-    torch::Tensor bt;
-    if (paged) bt = block_table->stride(1) == 1 ? *block_table : block_table->contiguous();
+    torch::Tensor bt;  // (undefined: the dense cache)
+    if (paged) bt = table_with_contiguous_rows(*block_table);
 
     if (fp8) {  // the quantizing kernel moves 16 bytes per load: inputs that are not so aligned are copied
         if (k.has_value()) {
@@ -1041,37 +1122,12 @@ std::tuple<torch::Tensor, torch::Tensor> kvcache_append_impl(
         p.qo_head_stride = stride_or_zero(q_rot, 1);
         p.qo_seqlen_stride = stride_or_zero(q_rot, 2);
     }
-    if (cs.defined()) {
-        p.cos = cs.data_ptr();
-        p.sin = sn_t.data_ptr();
-        p.cs_row_stride = stride_or_zero(cs, 0);
-        p.max_pos = cs.size(0);
-    }
-    p.k_cache = k_cache.data_ptr();
-    p.v_cache = v_cache.data_ptr();
-    p.k_page_stride = stride_or_zero(k_cache, 0);
-    p.k_head_stride = stride_or_zero(k_cache, 1);
-    p.k_row_stride = stride_or_zero(k_cache, 2);
-    p.v_page_stride = stride_or_zero(v_cache, 0);
-    p.v_head_stride = stride_or_zero(v_cache, 1);
-    p.v_row_stride = stride_or_zero(v_cache, 2);
-    p.block_table = paged ? bt.data_ptr<int32_t>() : nullptr;
-    p.block_table_stride = paged ? bt.stride(0) : 0;
-    p.max_pages = max_pages;
-    p.num_pages = k_cache.size(0);
-    p.page_size = page_size;
-    p.seqlens_k = sl.data_ptr<int32_t>();
-    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
-    p.batch_size = bs;
+    fill_append_cache(p, k_cache, v_cache, bt, sl, new_seqlens, cs, sn_t);
     p.num_heads_q = hq;
-    p.num_heads_kv = hkv;
     p.seqlen_new = sn;
     p.seqlen_q = sq;
-    p.headdim = d;
     if (fp8) {
-        torch::Tensor keep_k, keep_v;
-        fill_descales(*fp8, k_cache, bs, hkv, fp.k_descale, fp.v_descale, fp.descale_batch_stride,
-                      fp.descale_head_stride, keep_k, keep_v);
+        const auto descales = fill_descales(fp, *fp8, k_cache, bs, hkv);
         const int dtype = io_dtype == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16;
         check_rc(fa_kvcache_append_fp8_gfx950(&fp, dtype, current_stream(k_cache)), "fa_kvcache_append_fp8_gfx950");
         return {new_seqlens, q_rot};
@@ -1092,7 +1148,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_fp8(
     torch::Tensor &cache_seqlens, c10::optional<torch::Tensor> block_table, c10::optional<torch::Tensor> q,
     c10::optional<torch::Tensor> rotary_cos, c10::optional<torch::Tensor> rotary_sin,
     c10::optional<torch::Tensor> k_descale, c10::optional<torch::Tensor> v_descale) {
-    const Fp8Descales ds{k_descale.has_value() ? &*k_descale : nullptr, v_descale.has_value() ? &*v_descale : nullptr};
+    const Fp8Descales ds = descales_of(k_descale, v_descale);
     return kvcache_append_impl(k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos, rotary_sin, &ds);
 }
 
@@ -1106,14 +1162,11 @@ torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &
                                                torch::Tensor &block_table, torch::Tensor &cache_seqlens,
                                                int64_t window_left, float softmax_scale, bool causal) {
     TORCH_CHECK(q.dim() == 3, "ragged q must be 3-D [total_q, heads, dim]");
-    TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4, "the caches must be 4-D [pages, heads, page_size, dim]");
-    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k_cache, v_cache must have the same shape");
+    check_pools(k_cache, v_cache, kPagedRagged);
     TORCH_CHECK(q.size(2) == k_cache.size(3), "q and the caches must have the same hidden dimension");
     TORCH_CHECK(q.size(1) > 0 && q.size(2) > 0, "q must have at least one head and one element per row");
-    TORCH_CHECK(k_cache.size(0) > 0 && k_cache.size(1) > 0, "the caches must have at least one page and one head");
     TORCH_CHECK(q.size(1) % k_cache.size(1) == 0,
                 "number of heads in q must be multiple of number of heads in k and v");
-    TORCH_CHECK(k_cache.size(2) > 0 && k_cache.size(2) % 64 == 0, "page_size must be a positive multiple of 64");
     check_dtype(q, k_cache, v_cache);
     TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
                 "q, k, v must be contiguous in the last dimension");
@@ -1122,15 +1175,7 @@ torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &
                 "cu_seqlens_q must be int32 with batch_size + 1 entries");
     const int64_t bs = cu_seqlens_q.size(0) - 1;
     TORCH_CHECK(cu_seqlens_q.device() == q.device(), "cu_seqlens_q must be on the device of q");
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
-                    block_table.size(1) > 0,
-                "block_table must be int32 [batch, max_pages]");
-    TORCH_CHECK(block_table.device() == q.device(), "block_table must be on the device of q");
-    TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) == 1,
-                "block_table rows must be contiguous (the table is read in place)");
-    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
-                "cache_seqlens must be int32 [batch]");
-    TORCH_CHECK(cache_seqlens.device() == q.device(), "cache_seqlens must be on the device of q");
+    PagedCache cache = paged_cache(k_cache, v_cache, block_table, cache_seqlens, bs, q.device(), kPagedRagged);
     TORCH_CHECK(max_seqlen_q >= 0, "max_seqlen_q must be non-negative");
     c10::DeviceGuard device_guard(q.device());
     require_gfx950(q.device());
@@ -1138,57 +1183,34 @@ torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &
     auto o = torch::empty_like(q);
     // nothing to launch: no row, no q-tile, or an empty step (batch 0, as the append and the C ABI take it)
     if (q.size(0) == 0 || max_seqlen_q == 0 || bs == 0) return o;
-    auto aligned_rows = [](const torch::Tensor &t) {
-        return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && (t.stride(0) % 8 == 0 || t.size(0) <= 1) &&
-               (t.stride(1) % 8 == 0 || t.size(1) <= 1);
-    };
     torch::Tensor qx = aligned_rows(q) ? q : q.contiguous();
     if (!aligned_rows(o) || o.stride(2) != 1) o = torch::empty(q.sizes(), q.options());
-    torch::Tensor kx = aligned_or_contiguous(k_cache), vx = aligned_or_contiguous(v_cache);
-    torch::Tensor cq = cu_seqlens_q.contiguous(), sl = cache_seqlens.contiguous();
+    torch::Tensor cq = cu_seqlens_q.contiguous();
 
     fa_paged_varlen_params vp;
     memset(&vp, 0, sizeof(vp));
     fa_paged_params &pp = vp.paged;
     fa_fwd_params &params = pp.base;
-    params.q_ptr = qx.data_ptr();
-    params.k_ptr = kx.data_ptr();
-    params.v_ptr = vx.data_ptr();
-    params.o_ptr = o.data_ptr();
-    params.batch_size = bs;
-    params.num_heads_q = qx.size(1);
-    params.num_heads_kv = kx.size(1);
-    params.seqlen_q = max_seqlen_q;
-    params.seqlen_kv = block_table.size(1) * kx.size(2);
-    params.headdim = qx.size(2);
-    params.head_q_per_group = qx.size(1) / kx.size(1);
-    params.q_head_stride = qx.size(1) == 1 ? 0 : qx.stride(1);
-    params.o_head_stride = o.size(1) == 1 ? 0 : o.stride(1);
+    // (of the pools, fill_packed_params keeps the head count; fill_paged writes every other k / v field)
+    fill_packed_params(params, qx, k_cache, v_cache, o, bs, max_seqlen_q, 0, softmax_scale);
+    fill_paged(pp, cache);
+    // The library checks q / o with the dense entry's rules -- every stride a multiple of 8, max_seqlen_q rows one
+    // row stride apart -- also along a dimension of size 1, which in torch may carry any stride: a single head gets
+    // 0 and a single row the dense row size. (flash_attention_varlen_fwd passes such strides as they are.)
+    params.q_head_stride = stride_or_zero(qx, 1);
+    params.o_head_stride = stride_or_zero(o, 1);
     params.q_seqlen_stride = qx.size(0) == 1 ? qx.size(1) * qx.size(2) : qx.stride(0);
     params.o_seqlen_stride = o.size(0) == 1 ? o.size(1) * o.size(2) : o.stride(0);
-    params.k_batch_stride = stride_or_zero(kx, 0);  // (the page stride)
-    params.v_batch_stride = stride_or_zero(vx, 0);
-    params.k_head_stride = stride_or_zero(kx, 1);
-    params.v_head_stride = stride_or_zero(vx, 1);
-    params.k_seqlen_stride = kx.stride(2);
-    params.v_seqlen_stride = vx.stride(2);
-    softmax_scale *= M_LOG2E;
-    params.softmax_scale = softmax_scale;
-    pp.block_table = block_table.data_ptr<int32_t>();
-    pp.block_table_stride = block_table.stride(0);
-    pp.max_pages = block_table.size(1);
-    pp.num_pages = kx.size(0);
-    pp.page_size = kx.size(2);
-    pp.seqlens_k = sl.data_ptr<int32_t>();
     vp.cu_seqlens_q = cq.data_ptr<int32_t>();
     vp.total_q = qx.size(0);
-    const int dtype = fa_dtype(qx);
-    const int64_t ws_bytes = fa_fwd_gfx950_paged_varlen_workspace_size(&vp, dtype, causal ? 1 : 0, window_left);
-    TORCH_CHECK(ws_bytes >= 0, "fa_fwd_gfx950_paged_varlen_workspace_size failed: ", fa_last_error());
-    torch::Tensor ws = workspace_for(ws_bytes, qx.options());
-    check_rc(fa_fwd_gfx950_paged_varlen(&vp, dtype, causal ? 1 : 0, window_left, data_or_null(ws), ws_bytes,
-                                        current_stream(qx)),
-             "fa_fwd_gfx950_paged_varlen");
+    const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    launch_with_workspace(
+        "fa_fwd_gfx950_paged_varlen",
+        [&] { return fa_fwd_gfx950_paged_varlen_workspace_size(&vp, dtype, c, window_left); },
+        [&](void *ws, int64_t ws_bytes) {
+            return fa_fwd_gfx950_paged_varlen(&vp, dtype, c, window_left, ws, ws_bytes, current_stream(qx));
+        },
+        qx.options());
     return o;
 }
 
@@ -1222,9 +1244,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
     const int64_t hkv = k_cache.size(1), d = k_cache.size(3);
     TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && bs >= 0, "cache_seqlens must be int32 [batch]");
     TORCH_CHECK(cache_seqlens.device() == dev, "cache_seqlens must be on the device of the caches");
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == bs &&
-                    block_table.size(1) > 0,
-                "block_table must be int32 [batch, max_pages]");
+    check_table(block_table, bs);
     TORCH_CHECK(block_table.device() == dev, "block_table must be on the device of the caches");
     auto check_cu = [&](const torch::Tensor &t, const char *name) {
         TORCH_CHECK(t.dtype() == torch::kInt32 && t.dim() == 1 && t.size(0) == bs + 1, name,
@@ -1247,22 +1267,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
         check_rows(*q, "q", hkv);
     }
     torch::Tensor cs, sn_t;
-    if (rotary_cos.has_value()) {
-        TORCH_CHECK(d % 2 == 0, "RoPE needs an even head dimension");
-        auto table = [&](const torch::Tensor &t, const char *name) {
-            TORCH_CHECK(t.dim() == 2 && t.size(0) > 0 && t.size(1) == d, name, " must be [max_pos, ", d, "]");
-            TORCH_CHECK(t.dtype() == k_cache.dtype(), name, " must have the caches' data type");
-            TORCH_CHECK(t.device() == dev, name, " must be on the device of the caches");
-            return t.stride(1) == 1 ? t : t.contiguous();
-        };
-        cs = table(*rotary_cos, "rotary_cos");
-        sn_t = table(*rotary_sin, "rotary_sin");
-        TORCH_CHECK(cs.size(0) == sn_t.size(0), "rotary_cos and rotary_sin must have the same number of rows");
-        if (cs.size(0) > 1 && cs.stride(0) != sn_t.stride(0)) {
-            cs = cs.contiguous();
-            sn_t = sn_t.contiguous();
-        }
-    }
+    std::tie(cs, sn_t) = append_rope_tables(rotary_cos, rotary_sin, d, k_cache.dtype(), dev,
+                                            " must have the caches' data type");
     c10::DeviceGuard device_guard(dev);
     require_gfx950(dev);
 
@@ -1271,7 +1277,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
     torch::Tensor sl = cache_seqlens.contiguous();
     torch::Tensor new_seqlens = torch::empty({bs}, sl.options());
     if (bs == 0) return {new_seqlens, q_rot};
-    torch::Tensor bt = block_table.stride(1) == 1 ? block_table : block_table.contiguous();
+    torch::Tensor bt = table_with_contiguous_rows(block_table);
     torch::Tensor cn = cu_seqlens_new.contiguous(), cq;
 
     fa_kvcache_varlen_params p;
@@ -1298,30 +1304,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
         p.qo_head_stride = stride_or_zero(q_rot, 1);
         p.num_heads_q = q->size(1);
     }
-    if (cs.defined()) {
-        p.cos = cs.data_ptr();
-        p.sin = sn_t.data_ptr();
-        p.cs_row_stride = stride_or_zero(cs, 0);
-        p.max_pos = cs.size(0);
-    }
-    p.k_cache = k_cache.data_ptr();
-    p.v_cache = v_cache.data_ptr();
-    p.k_page_stride = stride_or_zero(k_cache, 0);
-    p.k_head_stride = stride_or_zero(k_cache, 1);
-    p.k_row_stride = stride_or_zero(k_cache, 2);
-    p.v_page_stride = stride_or_zero(v_cache, 0);
-    p.v_head_stride = stride_or_zero(v_cache, 1);
-    p.v_row_stride = stride_or_zero(v_cache, 2);
-    p.block_table = bt.data_ptr<int32_t>();
-    p.block_table_stride = bt.stride(0);
-    p.max_pages = bt.size(1);
-    p.num_pages = k_cache.size(0);
-    p.page_size = k_cache.size(2);
-    p.seqlens_k = sl.data_ptr<int32_t>();
-    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
-    p.batch_size = bs;
-    p.num_heads_kv = hkv;
-    p.headdim = d;
+    fill_append_cache(p, k_cache, v_cache, bt, sl, new_seqlens, cs, sn_t);
     check_rc(fa_kvcache_append_varlen_gfx950(&p, fa_dtype(k_cache), current_stream(k_cache)),
              "fa_kvcache_append_varlen_gfx950");
     return {new_seqlens, q_rot};
