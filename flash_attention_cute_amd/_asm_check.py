@@ -403,7 +403,11 @@ def check_file(path) -> list[str]:
     for inst, kernel in (("fa_paged_window_inst", "fa_decode_paged_window"),  # (the sliding-window variants)
                          ("fa_paged_fp8_window_inst", "fa_decode_fp8kv_window"),
                          ("fa_paged_lse_inst", "fa_decode_paged_lse"),  # (the LSE variants)
-                         ("fa_paged_fp8_lse_inst", "fa_decode_fp8kv_lse")):
+                         ("fa_paged_fp8_lse_inst", "fa_decode_fp8kv_lse"),
+                         ("fa_paged_sink_inst", "fa_decode_paged_sink"),  # (the attention-sink variants)
+                         ("fa_paged_fp8_sink_inst", "fa_decode_fp8kv_sink"),
+                         ("fa_paged_window_sink_inst", "fa_decode_paged_window_sink"),
+                         ("fa_paged_fp8_window_sink_inst", "fa_decode_fp8kv_window_sink")):
         if inst in str(path):
             if kernel not in text:
                 return [f"{path}: no {kernel} kernel in the assembly (stale or wrong file)"]

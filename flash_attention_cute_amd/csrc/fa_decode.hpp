@@ -38,6 +38,8 @@
 // (scripts/compare_decode_objs.py against the previous build, profiles/decode_unify_ab.json).
 // Two more kernels, fa_decode_paged_lse and fa_decode_fp8kv_lse (fa_decode_paged_lse.hpp), are the same body over
 // argument structs that carry an LSE output: `if constexpr (DecLse<Args>::value)` below, absent from the five.
+// Four more (fa_decode_paged_sink.hpp) are the paged four over argument structs that carry attention sinks:
+// `if constexpr (DecSink<Args>::value)`, at the same three final-row sites and absent from all the others.
 #include "fa_fwd_kernels.hpp"
 
 namespace fa {
@@ -86,6 +88,36 @@ __device__ __forceinline__ void decode_store_lse(const fa_fwd_params &p, const L
     *dst = L > 0.f ? __float_as_uint(v) : 0xff800000u;
 }
 
+// The sink variant (fa_decode_paged_sink.hpp): an argument struct with a member `sinks` (const float *, one fp32
+// logit per q-head, in final-logit units) makes the three places that produce a final row -- the unsplit
+// epilogue, the fused merge and fa_decode_combine_sink -- add one key of that logit and value 0 to the row's
+// softmax. Compile-time, as the LSE is: the kernels whose arguments carry no `sinks` compile without any of it.
+template <class A, class = void>
+struct DecSink : std::false_type {};
+template <class A>
+struct DecSink<A, std::void_t<decltype(std::declval<const A &>().sinks)>> : std::true_type {};
+
+// What replaces num / L for a row of q-head hq whose state is (M, L), M in log2 units: with s2 = sinks[hq] log2 e,
+// Ms = max(M, s2) and e = 2^(M - Ms), the row's sum becomes L' = L e + 2^(s2 - Ms) and its acc is scaled by
+// e num / L'. The max is taken first, so neither exp2 can overflow. The sink's magnitude is clamped to |kNeg| on
+// its BITS (-inf and +-3e38 included: no infinity enters float arithmetic, the build is -ffinite-math-only); a
+// sink that far below every score has e == 1 and L' == L exactly, and e * (num / L') is then the unsinked
+// division bit for bit. A row without a visible key (L == 0) stays 0. The load is a vector load: callers stand
+// behind the key loop's last s_waitcnt vmcnt(0), whose counted waits it would break.
+// No contraction in here: fused into fma(sink, log2 e, -Ms), the difference s2 - Ms is the rounding error of s2
+// when s2 is the max -- half an ulp of 1.4e30 for a clamped sink, far outside exp2's range, instead of 0.
+__device__ __forceinline__ float decode_sink_inv(const float *sinks, const int hq, const float M, const float L,
+                                                 const float num) {
+#pragma clang fp contract(off)
+    const uint32_t u = *(const uint32_t *)(sinks + hq);
+    const uint32_t mag = min(u & 0x7fffffffu, __float_as_uint(-kNeg));
+    const float s2 = __uint_as_float(mag | (u & 0x80000000u)) * 1.4426950408889634f;
+    const float Ms = fmaxf(M, s2);
+    const float e = __builtin_amdgcn_exp2f(M - Ms);
+    const float Ls = __builtin_fmaf(L, e, __builtin_amdgcn_exp2f(s2 - Ms));
+    return L > 0.f ? e * (num / Ls) : 0.f;
+}
+
 // Fused merge of a unit's n_split partials by the last of its workgroups (fa_decode, a.cnt): the same
 // arithmetic as fa_decode_combine (weights 2^(lse - M) in split order, acc / L), spread over the
 // workgroup: lse of every (split, row) into LDS, each row's weights by one thread, then a float4 of
@@ -113,7 +145,10 @@ __device__ __forceinline__ void decode_merge(const fa_fwd_params &p, const A &a,
             L += w;
             wt[s][tid] = w;
         }
-        linv[tid] = L > 0.f ? 1.f / L : 0.f;
+        if constexpr (DecSink<A>::value)  // the partials are unsinked: the sink enters here, once per row
+            linv[tid] = decode_sink_inv(a.sinks, hkv * a.g + (rb * kDecRows + tid) / (int)p.seqlen_q, M, L, 1.f);
+        else
+            linv[tid] = L > 0.f ? 1.f / L : 0.f;
         if constexpr (DecLse<A>::value) decode_store_lse(p, a.lse, a.g, b, hkv, rb * kDecRows + tid, M, L);
     }
     __syncthreads();
@@ -657,7 +692,13 @@ __device__ __forceinline__ void decode_body(const fa_fwd_params &p, const typena
     const float inv = L > 0.f ? vds / L : 0.f;
     const int rg2 = w.rb * kDecRows + row;
     if (a.n_split == 1) {
-        if (rg2 < a.rows) decode_store_o<DT, kD, kExactD>(p, a, w, rg2, part, acc, inv);
+        if constexpr (DecSink<typename Kv::Args>::value) {
+            if (rg2 < a.rows)
+                decode_store_o<DT, kD, kExactD>(p, a, w, rg2, part, acc,
+                                                decode_sink_inv(a.sinks, w.hkv * a.g + rg2 / Sq, M, L, vds));
+        } else {
+            if (rg2 < a.rows) decode_store_o<DT, kD, kExactD>(p, a, w, rg2, part, acc, inv);
+        }
         if constexpr (DecLse<typename Kv::Args>::value)
             if (rg2 < a.rows && part == 0) decode_store_lse(p, a.lse, a.g, w.b, w.hkv, rg2, M, L);
     } else {
@@ -675,10 +716,12 @@ __global__ __launch_bounds__(256, 1) void fa_decode(const fa_fwd_params p, const
 // position) row of a (batch, kv-head) -- a workgroup covers 4 of its a.rows rows, so the grid holds
 // only valid rows (B * Hkv * ceil(rows / 4) workgroups) -- lane l owns d = 2l, 2l+1 (kD = 128) or
 // d = l (kD = 64), so every partial row is one contiguous 512 / 256-B wave read.
-// (kLse, fa_decode_combine_lse: lane 0 also writes the row's lse to `lse`)
+// (kLse, fa_decode_combine_lse: lane 0 also writes the row's lse to `lse`; kSink, fa_decode_combine_sink: the
+// row's sink, `sinks`[q-head], joins its sum -- decode_sink_inv, once per row, the partials are unsinked)
 struct NoLse {};
-template <class DT, int kD, bool kExactD, bool kLse, class Lse>
-__device__ __forceinline__ void decode_combine_body(const fa_fwd_params &p, const DecArgs &a, const Lse &lse) {
+template <class DT, int kD, bool kExactD, bool kLse, class Lse, bool kSink = false>
+__device__ __forceinline__ void decode_combine_body(const fa_fwd_params &p, const DecArgs &a, const Lse &lse,
+                                                    const float *sinks = nullptr) {
     constexpr int DPL = kD / 64;  // d values per lane
     const int lane = threadIdx.x & 63;
     const int nb4 = (a.rows + 3) / 4;  // workgroups per (batch, kv-head)
@@ -710,8 +753,9 @@ __device__ __forceinline__ void decode_combine_body(const fa_fwd_params &p, cons
             acc[0] += w * src[0];
         }
     }
-    const float inv = L > 0.f ? 1.f / L : 0.f;
+    float inv = L > 0.f ? 1.f / L : 0.f;
     const int hq = hkv * a.g + rg / Sq, pos = rg % Sq;
+    if constexpr (kSink) inv = decode_sink_inv(sinks, hq, M, L, 1.f);
     char *orow = (char *)p.o_ptr +
                  2 * ((int64_t)b * p.o_batch_stride + (int64_t)hq * p.o_head_stride + (int64_t)pos * p.o_seqlen_stride);
     const int d = lane * DPL;
@@ -737,6 +781,12 @@ __global__ __launch_bounds__(256) void fa_decode_combine_lse(const fa_fwd_params
     decode_combine_body<DT, kD, kExactD, true>(p, a, lse);
 }
 
+template <class DT, int kD, bool kExactD>
+__global__ __launch_bounds__(256) void fa_decode_combine_sink(const fa_fwd_params p, const DecArgs a,
+                                                              const float *sinks) {
+    decode_combine_body<DT, kD, kExactD, false, NoLse, true>(p, a, NoLse{}, sinks);
+}
+
 // The launcher of every decode kernel (`fused` / `plain`: its two instantiations; `path` / `path_split`: what
 // fa_debug_last_path reports): the kernel, + the split combine when a.n_split > 1 and the merge is not fused
 template <class DT, int kD, bool kExact, class Args, class Kernel>
@@ -760,9 +810,13 @@ int launch_decode_kernels(const fa_fwd_params &p, Args a, void *ws, hipStream_t 
     hipLaunchKernelGGL(a.cnt ? fused : plain, dim3((uint32_t)grid), dim3(256), 0, stream, p, a);
     if (a.n_split > 1 && !a.cnt) {
         const dim3 cgrid((uint32_t)(p.batch_size * p.num_heads_kv * ((a.rows + 3) / 4)));
+        static_assert(!(DecLse<Args>::value && DecSink<Args>::value), "no kernel writes the LSE of a sinked row");
         if constexpr (DecLse<Args>::value)
             hipLaunchKernelGGL((fa_decode_combine_lse<DT, kD, kExact, decltype(a.lse)>), cgrid, dim3(256), 0, stream, p,
                                static_cast<const DecArgs &>(a), a.lse);
+        else if constexpr (DecSink<Args>::value)
+            hipLaunchKernelGGL((fa_decode_combine_sink<DT, kD, kExact>), cgrid, dim3(256), 0, stream, p,
+                               static_cast<const DecArgs &>(a), a.sinks);
         else
             hipLaunchKernelGGL((fa_decode_combine<DT, kD, kExact>), cgrid, dim3(256), 0, stream, p,
                                static_cast<const DecArgs &>(a));

@@ -37,6 +37,7 @@
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
 #include "fa_gfx950_paged_window.h"
+#include "fa_gfx950_sink.h"
 
 namespace flash_attention {
 
@@ -758,10 +759,23 @@ torch::Tensor flash_attention_padded_fwd(torch::Tensor &q, torch::Tensor &k, tor
 // goes to the windowed entries WITHOUT the q-head pack -- the window is relative to the real Sq, so a decode
 // step is passed as Sq 1 with g q-heads per kv-head (the same kernel rows and arithmetic as the pack, causal
 // dropped as the pack drops it); window_left < 0 is the unwindowed call, to the letter.
+//
+// sinks (flash_attention_paged_sink_fwd / _fp8_fwd, include/fa_gfx950_sink.h): fp32 [Hq] on q's device, one extra
+// softmax column per q-head of that logit and value 0; the sink entries, with or without a window, never with the
+// q-head pack (the pack loses the q-head a row belongs to).
 torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
                              torch::Tensor &block_table, torch::Tensor &cache_seqlens, float softmax_scale,
-                             bool causal, const Fp8Descales *fp8, int64_t window_left = -1, bool prefill = false) {
+                             bool causal, const Fp8Descales *fp8, int64_t window_left = -1, bool prefill = false,
+                             const torch::Tensor *sinks = nullptr) {
     check_q_and_pools(q, k_cache, v_cache, kPagedDecode);
+    torch::Tensor sinks_c;
+    if (sinks) {
+        TORCH_CHECK(!prefill, "the paged prefill kernel has no sinks");
+        TORCH_CHECK(sinks->dim() == 1 && sinks->size(0) == q.size(1) && sinks->dtype() == torch::kFloat32,
+                    "sinks must be fp32 [heads of q]");
+        TORCH_CHECK(sinks->device() == q.device(), "sinks must be on the device of q");
+        sinks_c = sinks->contiguous();
+    }
     if (fp8) {
         TORCH_CHECK(k_cache.dtype() == at::kFloat8_e4m3fn && v_cache.dtype() == at::kFloat8_e4m3fn,
                     "the fp8 caches must be torch.float8_e4m3fn");
@@ -779,13 +793,14 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     torch::Tensor qx = aligned_or_contiguous(q);
     const bool window = window_left >= 0;
     if (qx.size(2) == 1 && !prefill) {  // Sq == 1: the q-head pack of flash_attention_fwd (reference :64-83)
-        if (!window) qx = pack_head_q(qx, k_cache.size(1));
+        if (!window && !sinks) qx = pack_head_q(qx, k_cache.size(1));
         causal = false;
     }
     auto o = alloc_out_like(qx);
 
-    fa_paged_fp8_params fp;
-    memset(&fp, 0, sizeof(fp));
+    fa_paged_fp8_sink_params sp8;  // (the FP8 struct of the sink entries holds every other one)
+    memset(&sp8, 0, sizeof(sp8));
+    fa_paged_fp8_params &fp = sp8.fp8;
     fa_paged_params &pp = fp.paged;
     fill_params(pp.base, qx, k_cache, v_cache, o, softmax_scale);
     fill_paged(pp, cache);
@@ -794,13 +809,25 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
     std::pair<torch::Tensor, torch::Tensor> descales;
     if (fp8) descales = fill_descales(fp, *fp8, q, q.size(0), k_cache.size(1));
 
-    // one of five C entries, each with the size query of its name
-    enum Entry { kPrefill, kWindowFp8, kFp8, kWindow, kPlain };
+    // one of seven C entries, each with the size query of its name
+    enum Entry { kPrefill, kWindowFp8, kFp8, kWindow, kPlain, kSinkFp8, kSink };
     static const char *const names[] = {"fa_fwd_gfx950_paged_prefill", "fa_fwd_gfx950_paged_window_fp8",
-                                        "fa_fwd_gfx950_paged_fp8", "fa_fwd_gfx950_paged_window", "fa_fwd_gfx950_paged"};
-    const Entry entry = prefill ? kPrefill : fp8 ? (window ? kWindowFp8 : kFp8) : window ? kWindow : kPlain;
+                                        "fa_fwd_gfx950_paged_fp8", "fa_fwd_gfx950_paged_window", "fa_fwd_gfx950_paged",
+                                        "fa_fwd_gfx950_paged_sink_fp8", "fa_fwd_gfx950_paged_sink"};
+    const Entry entry = sinks     ? (fp8 ? kSinkFp8 : kSink)
+                        : prefill ? kPrefill
+                        : fp8     ? (window ? kWindowFp8 : kFp8)
+                        : window  ? kWindow
+                                  : kPlain;
     const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
     void *stream = current_stream(qx);
+    fa_paged_sink_params sp;
+    memset(&sp, 0, sizeof(sp));
+    if (sinks) {
+        sp8.sinks = sinks_c.data_ptr<float>();
+        sp.paged = pp;
+        sp.sinks = sp8.sinks;
+    }
     launch_with_workspace(
         names[entry],
         [&]() -> int64_t {
@@ -809,6 +836,8 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
                 case kWindowFp8: return fa_fwd_gfx950_paged_window_fp8_workspace_size(&fp, dtype, c, window_left);
                 case kFp8: return fa_fwd_gfx950_paged_fp8_workspace_size(&fp, dtype, c);
                 case kWindow: return fa_fwd_gfx950_paged_window_workspace_size(&pp, dtype, c, window_left);
+                case kSinkFp8: return fa_fwd_gfx950_paged_sink_fp8_workspace_size(&sp8, dtype, c, window_left);
+                case kSink: return fa_fwd_gfx950_paged_sink_workspace_size(&sp, dtype, c, window_left);
                 default: return fa_fwd_gfx950_paged_workspace_size(&pp, dtype, c);
             }
         },
@@ -818,6 +847,8 @@ torch::Tensor paged_fwd_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Te
                 case kWindowFp8: return fa_fwd_gfx950_paged_window_fp8(&fp, dtype, c, window_left, ws, ws_bytes, stream);
                 case kFp8: return fa_fwd_gfx950_paged_fp8(&fp, dtype, c, ws, ws_bytes, stream);
                 case kWindow: return fa_fwd_gfx950_paged_window(&pp, dtype, c, window_left, ws, ws_bytes, stream);
+                case kSinkFp8: return fa_fwd_gfx950_paged_sink_fp8(&sp8, dtype, c, window_left, ws, ws_bytes, stream);
+                case kSink: return fa_fwd_gfx950_paged_sink(&sp, dtype, c, window_left, ws, ws_bytes, stream);
                 default: return fa_fwd_gfx950_paged(&pp, dtype, c, ws, ws_bytes, stream);
             }
         },
@@ -862,6 +893,27 @@ torch::Tensor flash_attention_paged_window_fp8_fwd(torch::Tensor &q, torch::Tens
                                                    bool causal) {
     const Fp8Descales ds = descales_of(k_descale, v_descale);
     return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds, window_left);
+}
+
+// Paged decode with attention sinks (include/fa_gfx950_sink.h fa_fwd_gfx950_paged_sink / _sink_fp8): sinks fp32
+// [Hq] on q's device, window_left < 0 for no window. Decode shapes only (the library refuses g * Sq > 64).
+torch::Tensor flash_attention_paged_sink_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                             torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                             torch::Tensor &sinks, int64_t window_left, float softmax_scale,
+                                             bool causal) {
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, nullptr, window_left,
+                          false, &sinks);
+}
+
+torch::Tensor flash_attention_paged_sink_fp8_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                                 torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                                 torch::Tensor &sinks, int64_t window_left,
+                                                 c10::optional<torch::Tensor> k_descale,
+                                                 c10::optional<torch::Tensor> v_descale, float softmax_scale,
+                                                 bool causal) {
+    const Fp8Descales ds = descales_of(k_descale, v_descale);
+    return paged_fwd_impl(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, &ds, window_left,
+                          false, &sinks);
 }
 
 // Paged decode that also returns the softmax log-sum-exp (include/fa_gfx950_lse.h fa_fwd_gfx950_paged_lse /
@@ -1349,6 +1401,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_merge_states", &flash_attention::flash_attention_merge_states,
           "Merge partial attention states (outputs and log-sum-exps over disjoint key sets), one HIP pass (gfx950)");
     m.def("lse_version", []() { return fa_lse_version(); });
+    m.def("flash_attention_paged_sink_fwd", &flash_attention::flash_attention_paged_sink_fwd,
+          "Paged KV-cache decode with attention sinks (one extra softmax column per q-head), windowed or not, gfx950");
+    m.def("flash_attention_paged_sink_fp8_fwd", &flash_attention::flash_attention_paged_sink_fp8_fwd,
+          "Paged FP8 (e4m3) KV-cache decode with attention sinks, windowed or not, gfx950");
+    m.def("sink_version", []() { return fa_sink_version(); });
     m.def("flash_attention_paged_varlen_fwd", &flash_attention::flash_attention_paged_varlen_fwd,
           "Ragged (packed, cu_seqlens_q) query blocks over a 16-bit paged KV cache read in place, gfx950");
     m.def("paged_varlen_version", []() { return fa_paged_varlen_version(); });

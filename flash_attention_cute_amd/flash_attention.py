@@ -414,10 +414,28 @@ def flash_attention_paged_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cach
     return _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, -1)
 
 
-def _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, window_left):
+def _sdpa_with_sink(q, k, v, mask, softmax_scale, sinks):
+    """``_masked_sdpa`` with one extra softmax column per q-head, of logit ``sinks[h]`` (fp32 [Hq], final-logit
+    units: not scaled) and value 0, in fp32: the column is concatenated to the scaled, masked scores. Rows that see
+    no key are 0."""
+    g = q.size(1) // k.size(1)
+    scale = q.size(-1) ** -0.5 if softmax_scale is None else softmax_scale
+    s = torch.matmul(q.float(), k.float().repeat_interleave(g, dim=1).transpose(2, 3)) * scale  # [1, Hq, Sq, n]
+    if mask is not None:
+        s = s.masked_fill(~mask[None, None], float("-inf"))
+    col = sinks.float()[None, :, None, None].expand(s.size(0), -1, s.size(2), 1)
+    p = torch.softmax(torch.cat([s, col], dim=-1), dim=-1)[..., :-1]
+    p = torch.nan_to_num(p, nan=0.0)  # (a row whose every column is -inf)
+    o = torch.matmul(p, v.float().repeat_interleave(g, dim=1))
+    if mask is not None:
+        o = o.masked_fill(~mask.any(dim=1)[None, None, :, None], 0)
+    return o.to(q.dtype)
+
+
+def _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal, window_left, sinks=None):
     """The non-GPU default of the paged ops. With a window (``window_left >= 0``, ``_window_mask`` per
     sequence) the pages wholly below the sequence's first visible key are not gathered, as the kernel never
-    reads them or their table entries."""
+    reads them or their table entries. ``sinks`` (the sink ops): one extra softmax column per q-head."""
     out = torch.zeros_like(q)
     sq = q.size(2)
     num_pages, _, page_size, _ = k_cache.shape
@@ -435,7 +453,10 @@ def _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_sc
             mask = _window_mask(sq, n, window_left, causal, q.device)[:, k0:]
         else:
             mask = _bottom_right_causal(sq, n, q.device) if causal else None
-        out[b:b + 1] = _masked_sdpa(q[b:b + 1], kb, vb, mask, softmax_scale)
+        if sinks is not None:
+            out[b:b + 1] = _sdpa_with_sink(q[b:b + 1], kb, vb, mask, softmax_scale, sinks)
+        else:
+            out[b:b + 1] = _masked_sdpa(q[b:b + 1], kb, vb, mask, softmax_scale)
     return out
 
 
@@ -508,7 +529,7 @@ def flash_attention_paged_window_forward_fake(q, k_cache, v_cache, block_table, 
 
 
 def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale=None, causal=False,
-                          k_descale=None, v_descale=None, window_left=-1, return_lse=False):
+                          k_descale=None, v_descale=None, window_left=-1, return_lse=False, sinks=None):
     """Attention of q [B, Hq, Sq, D] -- each sequence's LAST Sq positions -- over a paged KV cache:
     ``k_cache`` / ``v_cache`` [num_pages, Hkv, page_size, D] with any strides (flash-attn's
     [num_pages, page_size, Hkv, D] is ``cache.transpose(1, 2)``), ``page_size`` a multiple of 32;
@@ -549,9 +570,24 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     FP8 cache the scale includes ``k_descale``, ``v_descale`` does not enter), ``-inf`` for a row without a
     visible key. ``out`` is bit-identical to the call without it. Decode shapes only and no window
     (``NotImplementedError`` otherwise), D a multiple of 8. Two such results over disjoint key sets combine
-    with ``flash_attn_merge_states``. The default runs the unchanged call."""
+    with ``flash_attn_merge_states``. The default runs the unchanged call.
+
+    ``sinks`` ([Hq] on q's device; fp32, or fp16 / bf16 converted once; ``ValueError`` for any other shape) are
+    attention sinks, flash-attn's ``s_aux`` / vLLM's ``sinks``, as the gpt-oss models have them: one learned logit
+    per q-head that joins the softmax denominator and contributes no value, ``out = (v_descale) sum_n exp(s_n - mu)
+    v_n / (sum_n exp(s_n - mu) + exp(sinks[h] - mu))`` with ``mu = max(max_n s_n, sinks[h])`` over the row's
+    visible keys. ``sinks`` is in final-logit units: NOT multiplied by ``softmax_scale`` or ``k_descale`` (HF's
+    eager gpt-oss semantics, the column concatenated to the scaled, masked scores). Both cache formats, with or
+    without ``window_left``; kernels of their own apply the sink once per row where the final row is produced
+    (in a split launch: in the merge). ``-inf`` (anything at or below -1e30) on a head means no sink there: that
+    head's rows have the bits of the call without ``sinks``. A row without a visible key stays 0. Decode shapes
+    only (``Hq / Hkv * Sq <= 64``), D a multiple of 8, and not with ``return_lse=True``
+    (``NotImplementedError`` each). ``sinks=None`` is the call above, bit for bit."""
     softmax_scale = _default_scale(q, softmax_scale)
     window_left = int(window_left)
+    if sinks is not None:
+        return _paged_sink(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, softmax_scale, causal,
+                           k_descale, v_descale, return_lse)
     if return_lse:
         return _paged_lse(q, k_cache, v_cache, block_table, cache_seqlens, 0, softmax_scale, causal, k_descale,
                           v_descale, window_left)
@@ -683,7 +719,7 @@ def flash_attn_kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None,
                             cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             return_seqlens=False, k_descale=None, v_descale=None, window_left=-1,
-                            shared_prefix_len=0):
+                            shared_prefix_len=0, sinks=None):
     """flash-attn's ``flash_attn_with_kvcache`` in this project's [B, H, S, D] layout: one serving step on
     a paged (``block_table`` given) or dense KV cache. When ``k`` / ``v`` [B, Hkv, Sn, D] are given they are
     appended in place at ``cache_seqlens`` (``flash_attn_kvcache_append``: the same drop rules); when the
@@ -711,9 +747,24 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     ``shared_prefix_len > 0`` runs the attention half as ``flash_attn_paged_shared_prefix_func(...,
     prefix_len=shared_prefix_len)`` over the advanced lengths (its contract applies): paged caches only, decode
     steps (``Sq == 1``) only, no window (``ValueError`` otherwise); the append is unchanged. The default 0 is the
-    call above, bit for bit."""
+    call above, bit for bit.
+
+    ``sinks`` ([Hq], see ``flash_attn_paged_func``) runs the attention half as ``flash_attn_paged_func(...,
+    sinks=sinks)`` over the advanced lengths; the append is unchanged. Only the paged decode kernels have sinks, so
+    a DENSE 16-bit cache [B, Hkv, Smax, D] is then read through an identity table as the dense FP8 cache is
+    (batch row b is page b, ``page_size = Smax``): ``Smax`` must be a multiple of 32, ``ValueError`` otherwise --
+    the padded kernels have no sinks and nothing is copied. Not with ``shared_prefix_len`` (``ValueError``).
+    ``sinks=None`` is the call above, bit for bit."""
     window_left = int(window_left)
     shared_prefix_len = int(shared_prefix_len)
+    if sinks is not None:
+        if shared_prefix_len:
+            raise ValueError("shared_prefix_len and sinks cannot be combined")
+        sinks = _sinks_arg(sinks, q)  # (the errors of the attention half, before anything is appended)
+        _check_sink_shape(q, k_cache)
+        if block_table is None and k_cache.size(2) % 32 != 0:
+            raise ValueError(f"with sinks a dense cache is read through the paged kernel: its length "
+                             f"({k_cache.size(2)}) must be a multiple of 32")
     if shared_prefix_len:
         if block_table is None:
             raise ValueError("shared_prefix_len applies to a paged cache (block_table) only")
@@ -746,7 +797,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         table = block_table
         if table is None:  # a dense cache: batch row b is page b
             table = torch.arange(b, dtype=torch.int32, device=q.device)[:, None]
-        if shared_prefix_len:
+        if sinks is not None:
+            out = _paged_sink(q_rot, k_cache, v_cache, table, new_seqlens, sinks, window_left, softmax_scale, causal,
+                              kd, vd)
+        elif shared_prefix_len:
             out = flash_attn_paged_shared_prefix_func(q_rot, k_cache, v_cache, table, new_seqlens, shared_prefix_len,
                                                       softmax_scale, causal, kd, vd)
         elif window_left >= 0:
@@ -761,7 +815,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
             k_cache, v_cache, k, v, cache_seqlens, block_table, q, rotary_cos.to(q.dtype), rotary_sin.to(q.dtype))
     elif k is not None:
         new_seqlens, _ = torch.ops.flash_attention.kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table)
-    if shared_prefix_len:
+    if sinks is not None:
+        table = block_table
+        if table is None:  # a dense cache: batch row b is page b
+            table = torch.arange(q.size(0), dtype=torch.int32, device=q.device)[:, None]
+        out = _paged_sink(q_rot, k_cache, v_cache, table, new_seqlens, sinks, window_left, softmax_scale, causal,
+                          None, None)
+    elif shared_prefix_len:
         out = flash_attn_paged_shared_prefix_func(q_rot, k_cache, v_cache, block_table, new_seqlens, shared_prefix_len,
                                                   softmax_scale, causal)
     elif block_table is not None:
@@ -842,7 +902,7 @@ def flash_attention_paged_forward_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_
 
 
 def _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale, causal,
-                         window_left):
+                         window_left, sinks=None):
     b, hkv = q.size(0), k_cache.size(1)
     g = q.size(1) // hkv
     kd = _descale_or_ones(k_descale, b, hkv, q.device).repeat_interleave(g, dim=1)[:, :, None, None]
@@ -850,7 +910,7 @@ def _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_desc
     scale = q.size(-1) ** -0.5 if softmax_scale is None else softmax_scale
     warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=3)
     out = _paged_reference(q.float() * kd, k_cache.float(), v_cache.float(), block_table, cache_seqlens, scale, causal,
-                           window_left)
+                           window_left, sinks)
     return (out * vd).to(q.dtype)
 
 
@@ -922,6 +982,122 @@ def flash_attention_paged_window_forward_fp8_cuda(q: torch.Tensor, k_cache: torc
 def flash_attention_paged_window_forward_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, window_left,
                                                   k_descale=None, v_descale=None, softmax_scale=None, causal=False):
     return torch.empty_like(q)
+
+
+# Attention sinks on the paged decode (include/fa_gfx950_sink.h fa_fwd_gfx950_paged_sink / _sink_fp8): ops of their
+# own beside the paged ops, whose schemas stay as they are. A sink is one learned logit per q-head (flash-attn's
+# ``s_aux``, vLLM's ``sinks``, the gpt-oss models') that joins the softmax denominator and contributes no value:
+#   out = (v_descale) sum_n exp(s_n - mu) v_n / (sum_n exp(s_n - mu) + exp(sinks[h] - mu)),  mu = max(max_n s_n, sinks[h])
+# with s_n the scaled, masked scores; ``sinks`` is in final-logit units (no softmax_scale, no k_descale).
+def _check_sink_shape(q, k_cache, return_lse=False):
+    """The wrapper errors of every call with sinks: the sink kernels serve decode shapes and return no LSE."""
+    if return_lse:
+        raise NotImplementedError("sinks with return_lse=True: no kernel writes the LSE of a sinked row")
+    g, sq = q.size(1) // k_cache.size(1), q.size(2)
+    if g * sq > _PAGED_DECODE_MAX_ROWS:
+        raise NotImplementedError(f"sinks are served for decode shapes only (Hq / Hkv * Sq <= "
+                                  f"{_PAGED_DECODE_MAX_ROWS}, got {g * sq}): the prefill kernels and the copying "
+                                  "path have no sinks")
+    if q.size(3) % 8 != 0:
+        raise NotImplementedError(f"the calls with sinks need a head dim that is a multiple of 8 (got {q.size(3)})")
+
+
+def _sinks_arg(sinks, q):
+    """``sinks`` as the ops take it: fp32 [Hq] on q's device (fp16 / bf16 converted once)."""
+    if not isinstance(sinks, torch.Tensor) or sinks.dim() != 1 or sinks.size(0) != q.size(1):
+        got = tuple(sinks.shape) if isinstance(sinks, torch.Tensor) else type(sinks).__name__
+        raise ValueError(f"sinks must be a tensor [Hq] = [{q.size(1)}] (got {got})")
+    if sinks.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"sinks must be fp32, fp16 or bf16 (got {sinks.dtype})")
+    if sinks.device != q.device:
+        raise ValueError(f"sinks must be on {q.device} (got {sinks.device})")
+    return sinks.float()
+
+
+def _paged_sink_cuda(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, k_descale, v_descale,
+                     softmax_scale, causal, fp8):
+    _require_ext()
+    _check_sink_shape(q, k_cache)  # (no quiet other path: the library would refuse these shapes as well)
+    qc = q if q.stride(-1) == 1 else q.contiguous()
+    window_left = min(int(window_left), _MAX_WINDOW)
+    if fp8:
+        return flash_attention_cuda.flash_attention_paged_sink_fp8_fwd(
+            qc, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, k_descale, v_descale, softmax_scale,
+            causal)
+    return flash_attention_cuda.flash_attention_paged_sink_fwd(qc, k_cache, v_cache, block_table, cache_seqlens, sinks,
+                                                               window_left, softmax_scale, causal)
+
+
+@torch.library.custom_op("flash_attention::paged_forward_sink", mutates_args=())
+def flash_attention_paged_forward_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                       block_table: torch.Tensor, cache_seqlens: torch.Tensor, sinks: torch.Tensor,
+                                       window_left: int = -1, softmax_scale: float = None,
+                                       causal: bool = False) -> torch.Tensor:
+    # paged_forward / paged_window_forward (window_left < 0: no window) with one extra softmax column per q-head of
+    # logit sinks[h] (fp32 [Hq]) and value 0. Non-GPU default: _paged_reference with that column.
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _paged_reference(q, k_cache, v_cache, block_table, cache_seqlens, softmax_scale, causal,
+                            min(int(window_left), _MAX_WINDOW), sinks)
+
+
+@torch.library.register_kernel("flash_attention::paged_forward_sink", "cuda")
+def flash_attention_paged_forward_sink_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                            block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                            sinks: torch.Tensor, window_left: int = -1, softmax_scale: float = None,
+                                            causal: bool = False) -> torch.Tensor:
+    return _paged_sink_cuda(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, None, None,
+                            softmax_scale, causal, False)
+
+
+@torch.library.register_fake("flash_attention::paged_forward_sink")
+def flash_attention_paged_forward_sink_fake(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left=-1,
+                                            softmax_scale=None, causal=False):
+    return torch.empty_like(q)
+
+
+@torch.library.custom_op("flash_attention::paged_forward_sink_fp8", mutates_args=())
+def flash_attention_paged_forward_sink_fp8(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                           block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                           sinks: torch.Tensor, window_left: int = -1,
+                                           k_descale: Optional[torch.Tensor] = None,
+                                           v_descale: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                           causal: bool = False) -> torch.Tensor:
+    # paged_forward_fp8 / paged_window_forward_fp8 with the sink column; the sink is not multiplied by k_descale
+    return _paged_fp8_reference(q, k_cache, v_cache, block_table, cache_seqlens, k_descale, v_descale, softmax_scale,
+                                causal, min(int(window_left), _MAX_WINDOW), sinks)
+
+
+@torch.library.register_kernel("flash_attention::paged_forward_sink_fp8", "cuda")
+def flash_attention_paged_forward_sink_fp8_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                                block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                                sinks: torch.Tensor, window_left: int = -1,
+                                                k_descale: Optional[torch.Tensor] = None,
+                                                v_descale: Optional[torch.Tensor] = None,
+                                                softmax_scale: float = None, causal: bool = False) -> torch.Tensor:
+    return _paged_sink_cuda(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, k_descale, v_descale,
+                            softmax_scale, causal, True)
+
+
+@torch.library.register_fake("flash_attention::paged_forward_sink_fp8")
+def flash_attention_paged_forward_sink_fp8_fake(q, k_cache, v_cache, block_table, cache_seqlens, sinks,
+                                                window_left=-1, k_descale=None, v_descale=None, softmax_scale=None,
+                                                causal=False):
+    return torch.empty_like(q)
+
+
+def _paged_sink(q, k_cache, v_cache, block_table, cache_seqlens, sinks, window_left, softmax_scale, causal, k_descale,
+                v_descale, return_lse=False):
+    """The call of every wrapper with ``sinks``: its errors, then the sink op of the cache's format."""
+    sinks = _sinks_arg(sinks, q)
+    _check_sink_shape(q, k_cache, return_lse)
+    if _is_fp8_cache(k_cache, v_cache, k_descale, v_descale):
+        b, hkv = q.size(0), k_cache.size(1)
+        kd = _descale_arg(k_descale, "k_descale", b, hkv, q.device)
+        vd = _descale_arg(v_descale, "v_descale", b, hkv, q.device)
+        return torch.ops.flash_attention.paged_forward_sink_fp8(q, k_cache, v_cache, block_table, cache_seqlens, sinks,
+                                                                window_left, kd, vd, softmax_scale, causal)
+    return torch.ops.flash_attention.paged_forward_sink(q, k_cache, v_cache, block_table, cache_seqlens, sinks,
+                                                        window_left, softmax_scale, causal)
 
 
 def _io_dtype(k, q):
