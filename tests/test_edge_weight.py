@@ -54,6 +54,7 @@ import zlib
 import pytest
 import torch
 
+from accuracy import attend, span  # noqa: F401  (moved there unchanged)
 from test_fp8_kvcache import NAN_BYTE, empty_pool, make_fp8_paged, quant
 from test_kvcache import new_tokens, rope_tables
 from test_gpu_parity import TOL
@@ -80,46 +81,9 @@ def dv(*ts):
 
 
 # ------------------------------------------------------------------------------------------------
-# the mask as key ranges, a float64 / honest-arithmetic reference on them, and the elementwise check
+# the elementwise check (the mask as key ranges ``span`` and the float64 / honest-arithmetic reference ``attend``
+# on them live in tests/accuracy.py)
 # ------------------------------------------------------------------------------------------------
-def span(ks, ke, sq, causal, w=-1, qs=None, qe=None):
-    """Query row m of sequence b sees the buffer rows [lo[b, m], hi[b, m]) (lo == hi == 0: none). Keys
-    [ks, ke), queries [qs, qe) of Sq (the sequence's LAST positions), bottom-right causal, window w >= 0:
-    key n visible iff n >= m + L - Sq_b - w (the semantics of include/fa_gfx950.h)."""
-    ks, ke = ks.long()[:, None], ke.long()[:, None]
-    qs = torch.zeros_like(ks) if qs is None else qs.long()[:, None]
-    qe = torch.full_like(ks, sq) if qe is None else qe.long()[:, None]
-    m = torch.arange(sq)[None] - qs
-    n_k, n_q = ke - ks, qe - qs
-    diag = n_k - n_q
-    hi = ks + (torch.minimum(n_k, m + diag + 1) if causal else n_k.expand(-1, sq))
-    lo = ks + ((m + diag - w).clamp(min=0) if w >= 0 else torch.zeros_like(m))
-    live = (m >= 0) & (m < n_q) & (hi > lo)
-    return torch.where(live, lo, 0), torch.where(live, hi, 0)
-
-
-def attend(q, k, v, lo, hi, scale, emul=None):
-    """softmax(scale q k^T) v with row (b, *, m) over buffer rows [lo[b, m], hi[b, m]) (none: 0). float64, or
-    (``emul`` a dtype) the honest kernel's arithmetic: fp32 scores, P rounded to the io dtype before P.V, an
-    fp32 row sum, the output rounded. Returns (out [B, Hq, Sq, D] float64, P [B, Hq, Sq, N])."""
-    b, hq, sq, d = q.shape
-    hkv, n = k.size(1), k.size(2)
-    g = hq // hkv
-    dt = torch.float64 if emul is None else torch.float32
-    s = torch.matmul(q.reshape(b, hkv, g * sq, d).to(dt), k.to(dt).transpose(-1, -2)) * scale
-    pos = torch.arange(n)
-    mask = ((pos >= lo[:, :, None]) & (pos < hi[:, :, None]))[:, None].repeat(1, 1, g, 1)  # [B, 1, g * Sq, N]
-    s = s.masked_fill(~mask, float("-inf"))
-    mx = s.amax(-1, keepdim=True)
-    p = torch.exp(s - torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx)))
-    l = p.sum(-1, keepdim=True)
-    pv = p.to(emul).to(dt) if emul is not None else p
-    o = torch.where(l > 0, torch.matmul(pv, v.to(dt)) / l.clamp(min=1e-30), torch.zeros((), dtype=dt))
-    if emul is not None:
-        o = o.to(emul)
-    return o.double().reshape(b, hq, sq, d), (p / l.clamp(min=1e-30)).reshape(b, hq, sq, n)
-
-
 def excess(got, ref, dtype):
     """err - (atol + rtol |ref|), elementwise: positive means outside the bound of TOL."""
     atol, rtol, _ = TOL[dtype]
