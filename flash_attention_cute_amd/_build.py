@@ -8,15 +8,17 @@ into the package directory so the artefacts travel with the repository snapshot.
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
      head-dim tile x exact-D instantiation, compiled in parallel) + the other INST_TUS x 16 (the paged
      decode kernels, the FP8 paged decode kernels, their sliding-window, LSE and attention-sink variants, the paged
-     fa_fwd_w4 and its ragged-query variant, the same combinations) + csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip,
-     csrc/fa_paged_prefill_gfx950.hip, csrc/fa_paged_lse_gfx950.hip, csrc/fa_paged_varlen_gfx950.hip,
-     csrc/fa_paged_sink_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip,
+     fa_fwd_w4, its ragged-query variant and that with attention sinks, the same combinations) +
+     csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip, csrc/fa_paged_prefill_gfx950.hip, csrc/fa_paged_lse_gfx950.hip,
+     csrc/fa_paged_varlen_gfx950.hip, csrc/fa_paged_sink_gfx950.hip, csrc/fa_paged_varlen_sink_gfx950.hip
+     (C-ABI dispatchers) + csrc/fa_rope.hip,
      csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip, csrc/fa_kvcache_varlen.hip, csrc/fa_merge.hip (stand-alone
      kernels with their entries)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
      include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h,
      include/fa_gfx950_paged_prefill.h, include/fa_gfx950_lse.h, include/fa_gfx950_paged_varlen.h,
-     include/fa_gfx950_kvcache_varlen.h and include/fa_gfx950_sink.h; no torch symbols)
+     include/fa_gfx950_kvcache_varlen.h, include/fa_gfx950_sink.h and include/fa_gfx950_paged_varlen_sink.h; no torch
+     symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -79,14 +81,20 @@ INSTANCES = [(dt, c, d, e) for dt in ("F16", "BF16") for c in (0, 1) for d in (6
 # The instantiation translation units: (directory prefix, csrc/<name>.hip), each compiled once per INSTANCES
 # entry into build/obj/<prefix><dtype>_c<causal>_d<tile>_x<exact>/ -- the dense kernels, the paged decode, its
 # FP8 pool, their sliding-window variants, the paged fa_fwd_w4 (the paged prefill), the paged decode / FP8 paged
-# decode that also write the LSE, the paged fa_fwd_w4 with ragged queries, and the four paged decodes with attention
-# sinks
+# decode that also write the LSE, the paged fa_fwd_w4 with ragged queries, that with attention sinks, and the four
+# paged decodes with attention sinks
 INST_TUS = (("", "fa_inst"), ("paged_", "fa_paged_inst"), ("fp8_", "fa_paged_fp8_inst"),
             ("win_", "fa_paged_window_inst"), ("win8_", "fa_paged_fp8_window_inst"),
             ("pfill_", "fa_paged_prefill_inst"), ("lse_", "fa_paged_lse_inst"), ("lse8_", "fa_paged_fp8_lse_inst"),
-            ("pvar_", "fa_paged_varlen_inst"), ("sink_", "fa_paged_sink_inst"),
+            ("pvar_", "fa_paged_varlen_inst"), ("pvars_", "fa_paged_varlen_sink_inst"),
+            ("sink_", "fa_paged_sink_inst"),
             ("sink8_", "fa_paged_fp8_sink_inst"), ("sinkw_", "fa_paged_window_sink_inst"),
             ("sinkw8_", "fa_paged_fp8_window_sink_inst"))
+
+# Instantiation files without debug / A-B bodies to select: their launchers pass dbg = 0, so -DFA_DEBUG_VARIANTS
+# would only add dead code to them. The debug library links the product library's objects of these (compiled once, in
+# build/obj/): each is a whole fa_fwd_w4 compile, the longest kind in the build.
+SHARED_WITH_DEBUG = ("fa_paged_varlen_sink_inst",)
 
 HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
              "-ffinite-math-only", "-fno-signed-zeros"]
@@ -122,7 +130,8 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
               defines: tuple = (), flags: tuple = (), only: tuple = (), debug: bool = False,
               gate: bool = True) -> Path:
     """Compile the HIP kernels + C-ABI into lib/libfa_gfx950.so (gfx950 code objects); ``debug``:
-    lib/libfa_gfx950_debug.so, the same with the debug / A-B kernel bodies (-DFA_DEBUG_VARIANTS).
+    lib/libfa_gfx950_debug.so, the same with the debug / A-B kernel bodies (-DFA_DEBUG_VARIANTS; the files of
+    SHARED_WITH_DEBUG have none and are the product's objects).
 
     Each kernel instantiation is its own translation unit (csrc/fa_inst.hip with -D selectors), so
     the 16 device compiles run in parallel; objects go to build/ and are linked by hipcc.
@@ -155,21 +164,22 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     for prefix, name in INST_TUS:
         for dt, c, d, e in INSTANCES:
             # one directory per instantiation: -save-temps=obj names its files after the source
-            idir = objdir / f"{prefix}{dt.lower()}_c{c}_d{d}_x{e}"
+            shared = debug and not diag and name in SHARED_WITH_DEBUG  # (the product's object and command)
+            idir = (ROOT / "build" / "obj" if shared else objdir) / f"{prefix}{dt.lower()}_c{c}_d{d}_x{e}"
             idir.mkdir(parents=True, exist_ok=True)
             obj = idir / f"{name}.o"
             objs.append(obj)
             stub = ["-DFA_INST_STUB=1"] if only and (dt, c, d, e) not in only else []
             if not stub:
                 asm_files.append(idir / f"{name}-hip-amdgcn-amd-amdhsa-{ARCH}.s")
-            cmds.append(([HIPCC, *HIP_FLAGS, *extra, *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
+            cmds.append(([HIPCC, *HIP_FLAGS, *([] if shared else extra), *stub, f"-I{INCLUDE}", f"-I{CSRC}", f"-DFA_INST_DT={dt}",
                           f"-DFA_INST_CAUSAL={c}", f"-DFA_INST_D={d}", f"-DFA_INST_EXACT={e}", "-save-temps=obj",
                           "-Wno-inline-asm", "-c", CSRC / f"{name}.hip", "-o", obj], obj,
                          inst_deps + [CSRC / f"{name}.hip"] + tooling))
     # C-ABI dispatchers (dense, paged decode, paged prefill, paged decode with LSE, ragged paged prefill, paged decode
-    # with sinks), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel
+    # with sinks, ragged paged prefill with sinks), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_paged_lse_gfx950.hip",
-                "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
+                "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
                 "fa_kvcache_varlen.hip", "fa_merge.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)

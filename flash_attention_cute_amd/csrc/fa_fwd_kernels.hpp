@@ -898,6 +898,39 @@ constexpr int vmcnt_enc(int n) { return (n & 15) | (((n >> 4) & 3) << 14) | 0x70
 #if FA_W4_PAGED_VARLEN && !FA_W4_PAGED
 #error "FA_W4_PAGED_VARLEN needs FA_W4_PAGED"
 #endif
+// FA_W4_SINK (fa_paged_varlen_sink.hpp sets it, with the two above, to 1): the ragged paged kernel with attention
+// SINKS -- it takes a PagedVarlenSinkArgs, and every row's softmax sum gets one more key of logit sinks[q-head]
+// and value 0, in the epilogue only. Translation units of its own again: at 0 this file preprocesses to what it was.
+#ifndef FA_W4_SINK
+#define FA_W4_SINK 0
+#endif
+#if FA_W4_SINK && !FA_W4_PAGED_VARLEN
+#error "FA_W4_SINK needs FA_W4_PAGED_VARLEN"
+#endif
+#if FA_W4_SINK
+// decode_sink_inv's arithmetic (fa_decode.hpp: its rules, restated where the sink is already in a register) on
+// fa_fwd_w4's state: a row's reference M = -nmsc in log2 units -- the reference of the deferred rescale, up to
+// kRescaleThr below the row's true max, which L is relative to -- and its whole sum L (after pair_sum). With s2 =
+// sink log2 e, Ms = max(M, s2) and e = 2^(M - Ms), the sum becomes L' = L e + 2^(s2 - Ms) and O is scaled by
+// e / L'. The max is taken first, so neither exp2 can overflow; the sink's magnitude is clamped to |kNeg| on its
+// BITS (-inf and +-3e38 included: no infinity enters float arithmetic, the build is -ffinite-math-only). A sink
+// that far below every score has e == 1 and L' == L exactly, and e * (1 / L') is then the unsinked 1 / L bit for
+// bit. A row without a visible key (L == 0) keeps the unsinked factor (its O is 0). No contraction: fused into
+// fma(sink, log2 e, -Ms), s2 - Ms would be s2's rounding error, not 0, when s2 is the max.
+__device__ __forceinline__ float w4_sink_inv(const uint32_t sink_bits, const float M, const float L) {
+#pragma clang fp contract(off)
+    const uint32_t mag = min(sink_bits & 0x7fffffffu, __float_as_uint(-kNeg));
+    // (the wave-uniform sink goes into a VGPR here: with it in an SGPR the multiply needs log2 e in a VGPR, which
+    // hipcc then keeps live across the whole key loop -- at D = 128 it was spilled into the O AGPRs)
+    float sink = __uint_as_float(mag | (sink_bits & 0x80000000u));
+    pin(sink);
+    const float s2 = sink * 1.4426950408889634f;
+    const float Ms = fmaxf(M, s2);
+    const float e = __builtin_amdgcn_exp2f(M - Ms);
+    const float Ls = __builtin_fmaf(L, e, __builtin_amdgcn_exp2f(s2 - Ms));
+    return (L == 0.f) ? 1.f : e * (1.f / Ls);
+}
+#endif
 #if FA_W4_PAGED
 // Where the K / V tiles of one Q block of sequence b live. A page holds tpp whole 64-key tiles, so tile t is
 // tile t % tpp of page row[t / tpp]. The pipelined loop issues K tile j + 1 and V tile j in iteration j --
@@ -976,7 +1009,13 @@ struct PagedTiles {
 // has been drained.
 // =============================================================================================
 template <class DT, bool kCausal, int kD, bool kExactD>
-#if FA_W4_PAGED_VARLEN  // (the same name, another argument struct: an overload the ragged translation units hold)
+#if FA_W4_SINK  // (the same name once more: the overload the sinked ragged translation units hold)
+__global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
+                                                          unsigned long long *stamps, const PathArgs xa,
+                                                          const PagedVarlenSinkArgs ps) {
+    const PagedPrefillArgs pg = ps.varlen.paged;
+    const int total_q = ps.varlen.total_q;
+#elif FA_W4_PAGED_VARLEN  // (the same name, another argument struct: an overload the ragged translation units hold)
 __global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
                                                           unsigned long long *stamps, const PathArgs xa,
                                                           const PagedVarlenArgs pv) {
@@ -1249,6 +1288,9 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // the packed query rows [q0, q0 + result) of sequence b (xa.q_rng = cu_seqlens_q, rng_hi = 1): q0 =
     // clamp(cu[b], 0, total_q), the end clamped into [q0, total_q], so a bad array never addresses outside q / o.
     // The index is made wave-uniform: the loads stay scalar and the block's descriptors stay in SGPRs.
+#if FA_W4_SINK
+    uint32_t sink_u = 0;  // (set_block: the bits of sinks[this block's q-head], wave-uniform)
+#endif
     auto q_rows_of = [&](const int b, int &q0) __attribute__((always_inline)) {
         const int bu = __builtin_amdgcn_readfirstlane(b);
         q0 = min(max(xa.q_rng[bu], 0), total_q);
@@ -1268,6 +1310,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
             qrow0 = (int64_t)q0 * p.q_seqlen_stride;
             orow0 = (int64_t)q0 * p.o_seqlen_stride;
         }
+#if FA_W4_SINK
+        // this block's sink: one q-head per block, so one value per wave. A scalar load through the constant
+        // space, here, where the block's q-head is decoded -- a vector load in the epilogue would sit inside the
+        // next prologue's counted vmcnt(kOStores), and its result would force a vmcnt(0) on the next block's DMA
+        sink_u = ((const __attribute__((address_space(4))) uint32_t *)ps.sinks)[__builtin_amdgcn_readfirstlane(hq)];
+#endif
 #else
         if (xa.q_rng) {  // this batch row's query rows and keys: absolute rows (the host zeroes the
                          // batch strides of ranged tensors; both ranges are given together here)
@@ -2311,6 +2359,9 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     char *const ob_c = ob;
     const int mw_c = mw, sq_c = Sq, jlo_c = j_lo, rowb_c = rowB, slot_c = split_slot;
     const bool spl_c = blk_split;
+#if FA_W4_SINK
+    const uint32_t sink_c = sink_u;  // (set_block below loads the NEXT block's)
+#endif
 #ifdef FA_STAMPS
     const uint32_t blk_c = xcd + 8 * kblk;
 #endif
@@ -2369,7 +2420,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
             o[2] = agpr_read16<ob0 + 32>();
             o[3] = agpr_read16<ob0 + 48>();
         }
+#if FA_W4_SINK  // (the caller passes the row's factor itself, w4_sink_inv: e / L' is no reciprocal of one number)
+        const float inv = l_tot;
+#else
         const float inv = (l_tot == 0.f) ? 1.f : 1.f / l_tot;
+#endif
         const int orow = row * os_ * 2;
 #pragma unroll
         for (int dt = 0; dt < DTL; ++dt) {
@@ -2468,8 +2523,18 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     [[maybe_unused]] int split_role = 0;  // (stamps) key-split piece: 1 the first to arrive, 3 the second
     if (!spl_c) {
         // row sums: each lane half summed half of the tile's keys
+#if FA_W4_SINK
+        // the sink joins the WHOLE row sum, once (before the pair sum it would count twice), and l0 / l1 are the
+        // factors store_block multiplies by
+#if FA_EPI_OVL
+#error "FA_W4_SINK: the deferred epilogue (FA_EPI_OVL) takes row sums, not factors"
+#endif
+        const float l0 = w4_sink_inv(sink_c, -st[0].nmsc, pair_sum(st[0].l));
+        const float l1 = w4_sink_inv(sink_c, -st[1].nmsc, pair_sum(st[1].l));
+#else
         const float l0 = pair_sum(st[0].l);
         const float l1 = pair_sum(st[1].l);
+#endif
 #if FA_EPI_OVL
         if (more) {  // the stores go into the next block's first tile (epi_unit)
             epi_pending = true;

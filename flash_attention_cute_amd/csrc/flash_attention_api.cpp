@@ -36,6 +36,7 @@
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
+#include "fa_gfx950_paged_varlen_sink.h"
 #include "fa_gfx950_paged_window.h"
 #include "fa_gfx950_sink.h"
 
@@ -1209,11 +1210,21 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_fp8(
 // cache_seqlens[b] keys; the pool read in place by the paged fa_fwd_w4 (page_size a multiple of 64). q is read in
 // place when its row and head strides are multiples of 8 and its base is 16-byte aligned (a slice of a fused QKV
 // projection), else made contiguous, as flash_attention_varlen_fwd does. No host synchronisation.
-torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
-                                               torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q,
-                                               torch::Tensor &block_table, torch::Tensor &cache_seqlens,
-                                               int64_t window_left, float softmax_scale, bool causal) {
+//
+// sinks (flash_attention_paged_varlen_sink_fwd, include/fa_gfx950_paged_varlen_sink.h): fp32 [Hq] on q's device, one
+// extra softmax column per q-head of that logit and value 0; the same steps, the sink entry.
+torch::Tensor paged_varlen_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q, torch::Tensor &block_table,
+                                torch::Tensor &cache_seqlens, int64_t window_left, float softmax_scale, bool causal,
+                                const torch::Tensor *sinks = nullptr) {
     TORCH_CHECK(q.dim() == 3, "ragged q must be 3-D [total_q, heads, dim]");
+    torch::Tensor sinks_c;
+    if (sinks) {
+        TORCH_CHECK(sinks->dim() == 1 && sinks->size(0) == q.size(1) && sinks->dtype() == torch::kFloat32,
+                    "sinks must be fp32 [heads of q]");
+        TORCH_CHECK(sinks->device() == q.device(), "sinks must be on the device of q");
+        sinks_c = sinks->contiguous();
+    }
     check_pools(k_cache, v_cache, kPagedRagged);
     TORCH_CHECK(q.size(2) == k_cache.size(3), "q and the caches must have the same hidden dimension");
     TORCH_CHECK(q.size(1) > 0 && q.size(2) > 0, "q must have at least one head and one element per row");
@@ -1256,6 +1267,20 @@ torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &
     vp.cu_seqlens_q = cq.data_ptr<int32_t>();
     vp.total_q = qx.size(0);
     const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    if (sinks) {
+        fa_paged_varlen_sink_params sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.varlen = vp;
+        sp.sinks = sinks_c.data_ptr<float>();
+        launch_with_workspace(
+            "fa_fwd_gfx950_paged_varlen_sink",
+            [&] { return fa_fwd_gfx950_paged_varlen_sink_workspace_size(&sp, dtype, c, window_left); },
+            [&](void *ws, int64_t ws_bytes) {
+                return fa_fwd_gfx950_paged_varlen_sink(&sp, dtype, c, window_left, ws, ws_bytes, current_stream(qx));
+            },
+            qx.options());
+        return o;
+    }
     launch_with_workspace(
         "fa_fwd_gfx950_paged_varlen",
         [&] { return fa_fwd_gfx950_paged_varlen_workspace_size(&vp, dtype, c, window_left); },
@@ -1264,6 +1289,25 @@ torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &
         },
         qx.options());
     return o;
+}
+
+torch::Tensor flash_attention_paged_varlen_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                               torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q,
+                                               torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                               int64_t window_left, float softmax_scale, bool causal) {
+    return paged_varlen_impl(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens, window_left,
+                             softmax_scale, causal);
+}
+
+// The same with attention sinks (include/fa_gfx950_paged_varlen_sink.h fa_fwd_gfx950_paged_varlen_sink): sinks fp32
+// [Hq] on q's device, any Sq_b, window_left < 0 for no window.
+torch::Tensor flash_attention_paged_varlen_sink_fwd(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
+                                                    torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q,
+                                                    torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                                    torch::Tensor &sinks, int64_t window_left, float softmax_scale,
+                                                    bool causal) {
+    return paged_varlen_impl(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens, window_left,
+                             softmax_scale, causal, &sinks);
 }
 
 // Ragged in-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache_varlen.h
@@ -1412,4 +1456,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_kvcache_append_varlen", &flash_attention::flash_attention_kvcache_append_varlen,
           "Ragged in-place append to a paged KV cache with fused rotate-half RoPE of k and q, one HIP launch (gfx950)");
     m.def("kvcache_varlen_version", []() { return fa_kvcache_varlen_version(); });
+    m.def("flash_attention_paged_varlen_sink_fwd", &flash_attention::flash_attention_paged_varlen_sink_fwd,
+          "Ragged query blocks over a 16-bit paged KV cache with attention sinks, windowed or not, gfx950");
+    m.def("paged_varlen_sink_version", []() { return fa_paged_varlen_sink_version(); });
 }

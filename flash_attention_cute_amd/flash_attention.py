@@ -582,7 +582,9 @@ def flash_attn_paged_func(q, k_cache, v_cache, block_table, cache_seqlens, softm
     (in a split launch: in the merge). ``-inf`` (anything at or below -1e30) on a head means no sink there: that
     head's rows have the bits of the call without ``sinks``. A row without a visible key stays 0. Decode shapes
     only (``Hq / Hkv * Sq <= 64``), D a multiple of 8, and not with ``return_lse=True``
-    (``NotImplementedError`` each). ``sinks=None`` is the call above, bit for bit."""
+    (``NotImplementedError`` each): a longer chunk with sinks, a uniform one too, goes through
+    ``flash_attn_paged_varlen_func(..., sinks=)`` with a uniform ``cu_seqlens_q`` (q packed [B * Sq, Hq, D]).
+    ``sinks=None`` is the call above, bit for bit."""
     softmax_scale = _default_scale(q, softmax_scale)
     window_left = int(window_left)
     if sinks is not None:
@@ -996,8 +998,9 @@ def _check_sink_shape(q, k_cache, return_lse=False):
     g, sq = q.size(1) // k_cache.size(1), q.size(2)
     if g * sq > _PAGED_DECODE_MAX_ROWS:
         raise NotImplementedError(f"sinks are served for decode shapes only (Hq / Hkv * Sq <= "
-                                  f"{_PAGED_DECODE_MAX_ROWS}, got {g * sq}): the prefill kernels and the copying "
-                                  "path have no sinks")
+                                  f"{_PAGED_DECODE_MAX_ROWS}, got {g * sq}): the uniform prefill kernels and the "
+                                  "copying path have no sinks; a longer chunk goes through "
+                                  "flash_attn_paged_varlen_func(..., sinks=) with a uniform cu_seqlens_q")
     if q.size(3) % 8 != 0:
         raise NotImplementedError(f"the calls with sinks need a head dim that is a multiple of 8 (got {q.size(3)})")
 
@@ -1511,17 +1514,11 @@ def _paged_varlen_unsupported(q, k_cache, v_cache):
                                   f"of 8: {alt}")
 
 
-@torch.library.custom_op("flash_attention::paged_varlen_forward", mutates_args=())
-def flash_attention_paged_varlen_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                                         cu_seqlens_q: torch.Tensor, max_seqlen_q: int, block_table: torch.Tensor,
-                                         cache_seqlens: torch.Tensor, softmax_scale: float = None,
-                                         causal: bool = False, window_left: int = -1) -> torch.Tensor:
-    # q: [total_q, Hq, D] packed; caches: [num_pages, Hkv, page_size, D]; cu_seqlens_q: int32 [B + 1];
-    # block_table: int32 [B, max_pages]; cache_seqlens: int32 [B]. Non-GPU default: a per-sequence loop in the
-    # style of _paged_reference (the sequence's pages gathered, torch SDPA under the kernel's masks, rows with
-    # no visible key 0, both arrays clamped as the kernel clamps them).
-    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
-    _paged_varlen_unsupported(q, k_cache, v_cache)
+def _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cache_seqlens, softmax_scale, causal,
+                            window_left, sinks=None):
+    """The non-GPU default of the ragged paged ops: a per-sequence loop in the style of ``_paged_reference`` (the
+    sequence's pages gathered, torch SDPA under the kernel's masks, rows with no visible key 0, both arrays clamped
+    as the kernel clamps them). ``sinks`` (the sink op): one extra softmax column per q-head."""
     window_left = min(int(window_left), _MAX_WINDOW)
     out = torch.zeros_like(q)
     num_pages, _, page_size, _ = k_cache.shape
@@ -1540,8 +1537,25 @@ def flash_attention_paged_varlen_forward(q: torch.Tensor, k_cache: torch.Tensor,
             mask = _window_mask(sq, n, window_left, causal, q.device)[:, k0:]
         else:
             mask = _bottom_right_causal(sq, n, q.device) if causal else None
-        out[q0:q1] = _masked_sdpa(q[q0:q1].transpose(0, 1)[None], kb, vb, mask, softmax_scale)[0].transpose(0, 1)
+        qb = q[q0:q1].transpose(0, 1)[None]
+        if sinks is not None:
+            out[q0:q1] = _sdpa_with_sink(qb, kb, vb, mask, softmax_scale, sinks)[0].transpose(0, 1)
+        else:
+            out[q0:q1] = _masked_sdpa(qb, kb, vb, mask, softmax_scale)[0].transpose(0, 1)
     return out
+
+
+@torch.library.custom_op("flash_attention::paged_varlen_forward", mutates_args=())
+def flash_attention_paged_varlen_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                         cu_seqlens_q: torch.Tensor, max_seqlen_q: int, block_table: torch.Tensor,
+                                         cache_seqlens: torch.Tensor, softmax_scale: float = None,
+                                         causal: bool = False, window_left: int = -1) -> torch.Tensor:
+    # q: [total_q, Hq, D] packed; caches: [num_pages, Hkv, page_size, D]; cu_seqlens_q: int32 [B + 1];
+    # block_table: int32 [B, max_pages]; cache_seqlens: int32 [B]. Non-GPU default: _paged_varlen_reference.
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    return _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cache_seqlens, softmax_scale,
+                                   causal, window_left)
 
 
 @torch.library.register_kernel("flash_attention::paged_varlen_forward", "cuda")
@@ -1565,8 +1579,45 @@ def flash_attention_paged_varlen_forward_fake(q, k_cache, v_cache, cu_seqlens_q,
     return torch.empty_like(q)
 
 
+# The same with attention sinks (include/fa_gfx950_paged_varlen_sink.h fa_fwd_gfx950_paged_varlen_sink): an op of its
+# own, so that paged_varlen_forward keeps its schema. ``sinks``: fp32 [Hq] on q's device, in final-logit units.
+@torch.library.custom_op("flash_attention::paged_varlen_forward_sink", mutates_args=())
+def flash_attention_paged_varlen_forward_sink(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                              cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                                              block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                              sinks: torch.Tensor, softmax_scale: float = None,
+                                              causal: bool = False, window_left: int = -1) -> torch.Tensor:
+    # Non-GPU default: _paged_varlen_reference with one extra softmax column per q-head (_sdpa_with_sink).
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    return _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cache_seqlens, softmax_scale,
+                                   causal, window_left, sinks)
+
+
+@torch.library.register_kernel("flash_attention::paged_varlen_forward_sink", "cuda")
+def flash_attention_paged_varlen_forward_sink_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                                   cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                                                   block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                                   sinks: torch.Tensor, softmax_scale: float = None,
+                                                   causal: bool = False, window_left: int = -1) -> torch.Tensor:
+    _require_ext()
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    return flash_attention_cuda.flash_attention_paged_varlen_sink_fwd(
+        q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), block_table, cache_seqlens, sinks,
+        min(int(window_left), _MAX_WINDOW), softmax_scale, causal)
+
+
+@torch.library.register_fake("flash_attention::paged_varlen_forward_sink")
+def flash_attention_paged_varlen_forward_sink_fake(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                                   cache_seqlens, sinks, softmax_scale=None, causal=False,
+                                                   window_left=-1):
+    return torch.empty_like(q)
+
+
 def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens,
-                                 softmax_scale=None, causal=False, window_left=-1):
+                                 softmax_scale=None, causal=False, window_left=-1, sinks=None):
     """Attention of RAGGED query blocks over a paged KV cache, in one launch: ``q`` [total_q, Hq, D] packed
     (flash-attn's varlen layout), sequence b owning rows ``[cu_seqlens_q[b], cu_seqlens_q[b + 1])`` (int32
     [B + 1] on q's device) -- its LAST ``Sq_b`` positions over ``L_b = clamp(cache_seqlens[b], 0, max_pages *
@@ -1593,13 +1644,28 @@ def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
     ONE-TOKEN SEQUENCE COSTS A WHOLE 256-ROW BLOCK. An engine should send its pure decode sequences to
     ``flash_attn_paged_func`` and only the sequences with prompt chunks here. 16-bit pools with ``page_size`` a
     multiple of 64 and D a multiple of 8 only (``NotImplementedError`` otherwise: call ``flash_attn_paged_func``
-    once per chunk length, or gather the pages for ``flash_attn_varlen_func``)."""
+    once per chunk length, or gather the pages for ``flash_attn_varlen_func``).
+
+    ``sinks`` (fp32 [Hq] on q's device; fp16 / bf16 are converted once; ``ValueError`` otherwise): attention
+    sinks, as in ``flash_attn_paged_func`` -- one learned logit per q-head, in final-logit units (not multiplied by
+    ``softmax_scale``), that joins every row's softmax denominator with value 0; ``-inf`` is no sink on that head
+    (the bits of the call without sinks), and a row without a visible key stays 0. Any ``Sq_b``: this is where a
+    prompt chunk of a model with sinks goes -- a UNIFORM chunk too, with a uniform ``cu_seqlens_q``, since
+    ``flash_attn_paged_func`` serves sinks for decode shapes only. ``None`` is the call without the argument, bit
+    for bit. The same layouts only: with FP8 pools, other page sizes or head dims it is ``NotImplementedError``
+    as above, and those alternatives have no sinks beyond decode shapes."""
     softmax_scale = _default_scale(q, softmax_scale)
+    if sinks is not None:
+        sinks = _sinks_arg(sinks, q)
     if _check_varlen_enabled():
         longest = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max()) if cu_seqlens_q.numel() > 1 else 0
         if longest > int(max_seqlen_q):
             raise ValueError(f"max_seqlen_q={int(max_seqlen_q)} is smaller than the longest sequence ({longest}) "
                              "in cu_seqlens_q")
+    if sinks is not None:
+        return torch.ops.flash_attention.paged_varlen_forward_sink(q, k_cache, v_cache, cu_seqlens_q,
+                                                                   int(max_seqlen_q), block_table, cache_seqlens,
+                                                                   sinks, softmax_scale, causal, int(window_left))
     return torch.ops.flash_attention.paged_varlen_forward(q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q),
                                                           block_table, cache_seqlens, softmax_scale, causal,
                                                           int(window_left))
@@ -1714,7 +1780,7 @@ def flash_attn_kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_new, cac
 def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, k=None, v=None,
                                    cu_seqlens_new=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                                    block_table=None, softmax_scale=None, causal=False, window_left=-1,
-                                   return_seqlens=False):
+                                   return_seqlens=False, sinks=None):
     """One step of a continuous batch on the paged cache, ``flash_attn_with_kvcache`` in the packed layout: the
     new ``k`` / ``v`` [total_new, Hkv, D] are appended in place at ``cache_seqlens``
     (``flash_attn_kvcache_append_varlen``; ``cu_seqlens_new`` defaults to ``cu_seqlens_q``, a step's new tokens
@@ -1722,9 +1788,16 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen
     each sequence's last ``Sq_b`` positions after the append, then q attends over the advanced lengths
     (``flash_attn_paged_varlen_func``, whose contract applies). Returns ``out`` [total_q, Hq, D], or ``(out,
     new_seqlens)`` with ``return_seqlens=True``; ``cache_seqlens`` is not modified. Two launches and no host
-    synchronisation, so the step can be captured in a graph."""
+    synchronisation, so the step can be captured in a graph.
+
+    ``sinks`` (fp32 [Hq], or ``None``): attention sinks in the attention half, as in
+    ``flash_attn_paged_varlen_func``; a bad ``sinks``, or a layout the sinked kernel does not read, is refused
+    before anything is appended."""
     if cache_seqlens is None or block_table is None:
         raise ValueError("flash_attn_varlen_with_kvcache needs cache_seqlens (int32 [batch]) and block_table")
+    if sinks is not None:
+        sinks = _sinks_arg(sinks, q)  # (the errors of the attention half, before anything is appended)
+        _paged_varlen_unsupported(q, k_cache, v_cache)
     if (k is None) != (v is None):
         raise ValueError("k and v must be given together")
     if (rotary_cos is None) != (rotary_sin is None):
@@ -1745,5 +1818,5 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen
             new_seqlens, _ = torch.ops.flash_attention.kvcache_append_varlen(
                 k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table)
     out = flash_attn_paged_varlen_func(q_rot, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, new_seqlens,
-                                       softmax_scale, causal, window_left)
+                                       softmax_scale, causal, window_left, sinks)
     return (out, new_seqlens) if return_seqlens else out
