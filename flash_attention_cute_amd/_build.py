@@ -8,17 +8,17 @@ into the package directory so the artefacts travel with the repository snapshot.
   1. ``hipcc --offload-arch=gfx950``  csrc/fa_inst.hip x 16 (one object per dtype x causal x
      head-dim tile x exact-D instantiation, compiled in parallel) + the other INST_TUS x 16 (the paged
      decode kernels, the FP8 paged decode kernels, their sliding-window, LSE and attention-sink variants, the paged
-     fa_fwd_w4, its ragged-query variant and that with attention sinks, the same combinations) +
+     fa_fwd_w4, its ragged-query variant, that with attention sinks and that with the LSE, the same combinations) +
      csrc/fa_fwd_gfx950.hip, csrc/fa_paged_gfx950.hip, csrc/fa_paged_prefill_gfx950.hip, csrc/fa_paged_lse_gfx950.hip,
-     csrc/fa_paged_varlen_gfx950.hip, csrc/fa_paged_sink_gfx950.hip, csrc/fa_paged_varlen_sink_gfx950.hip
-     (C-ABI dispatchers) + csrc/fa_rope.hip,
+     csrc/fa_paged_varlen_gfx950.hip, csrc/fa_paged_sink_gfx950.hip, csrc/fa_paged_varlen_sink_gfx950.hip,
+     csrc/fa_paged_varlen_lse_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip,
      csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip, csrc/fa_kvcache_varlen.hip, csrc/fa_merge.hip (stand-alone
      kernels with their entries)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
      include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h,
      include/fa_gfx950_paged_prefill.h, include/fa_gfx950_lse.h, include/fa_gfx950_paged_varlen.h,
-     include/fa_gfx950_kvcache_varlen.h, include/fa_gfx950_sink.h and include/fa_gfx950_paged_varlen_sink.h; no torch
-     symbols)
+     include/fa_gfx950_kvcache_varlen.h, include/fa_gfx950_sink.h, include/fa_gfx950_paged_varlen_sink.h and
+     include/fa_gfx950_paged_varlen_lse.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -81,12 +81,13 @@ INSTANCES = [(dt, c, d, e) for dt in ("F16", "BF16") for c in (0, 1) for d in (6
 # The instantiation translation units: (directory prefix, csrc/<name>.hip), each compiled once per INSTANCES
 # entry into build/obj/<prefix><dtype>_c<causal>_d<tile>_x<exact>/ -- the dense kernels, the paged decode, its
 # FP8 pool, their sliding-window variants, the paged fa_fwd_w4 (the paged prefill), the paged decode / FP8 paged
-# decode that also write the LSE, the paged fa_fwd_w4 with ragged queries, that with attention sinks, and the four
-# paged decodes with attention sinks
+# decode that also write the LSE, the paged fa_fwd_w4 with ragged queries, that with attention sinks, that with sinks and
+# the LSE, and the four paged decodes with attention sinks
 INST_TUS = (("", "fa_inst"), ("paged_", "fa_paged_inst"), ("fp8_", "fa_paged_fp8_inst"),
             ("win_", "fa_paged_window_inst"), ("win8_", "fa_paged_fp8_window_inst"),
             ("pfill_", "fa_paged_prefill_inst"), ("lse_", "fa_paged_lse_inst"), ("lse8_", "fa_paged_fp8_lse_inst"),
             ("pvar_", "fa_paged_varlen_inst"), ("pvars_", "fa_paged_varlen_sink_inst"),
+            ("pvarl_", "fa_paged_varlen_lse_inst"),
             ("sink_", "fa_paged_sink_inst"),
             ("sink8_", "fa_paged_fp8_sink_inst"), ("sinkw_", "fa_paged_window_sink_inst"),
             ("sinkw8_", "fa_paged_fp8_window_sink_inst"))
@@ -94,7 +95,7 @@ INST_TUS = (("", "fa_inst"), ("paged_", "fa_paged_inst"), ("fp8_", "fa_paged_fp8
 # Instantiation files without debug / A-B bodies to select: their launchers pass dbg = 0, so -DFA_DEBUG_VARIANTS
 # would only add dead code to them. The debug library links the product library's objects of these (compiled once, in
 # build/obj/): each is a whole fa_fwd_w4 compile, the longest kind in the build.
-SHARED_WITH_DEBUG = ("fa_paged_varlen_sink_inst",)
+SHARED_WITH_DEBUG = ("fa_paged_varlen_sink_inst", "fa_paged_varlen_lse_inst")
 
 HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
              "-ffinite-math-only", "-fno-signed-zeros"]
@@ -177,9 +178,10 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
                           "-Wno-inline-asm", "-c", CSRC / f"{name}.hip", "-o", obj], obj,
                          inst_deps + [CSRC / f"{name}.hip"] + tooling))
     # C-ABI dispatchers (dense, paged decode, paged prefill, paged decode with LSE, ragged paged prefill, paged decode
-    # with sinks, ragged paged prefill with sinks), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel
+    # with sinks, ragged paged prefill with sinks, ragged paged prefill with the LSE), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_paged_lse_gfx950.hip",
-                "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
+                "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip",
+                "fa_paged_varlen_lse_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
                 "fa_kvcache_varlen.hip", "fa_merge.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)

@@ -931,6 +931,44 @@ __device__ __forceinline__ float w4_sink_inv(const uint32_t sink_bits, const flo
     return (L == 0.f) ? 1.f : e * (1.f / Ls);
 }
 #endif
+// FA_W4_LSE (fa_paged_varlen_lse.hpp sets it, with the three above, to 1): the sinked ragged kernel that also
+// writes every owned row's softmax log-sum-exp -- it takes a PagedVarlenLseArgs, whose sinks may be NULL (the block's
+// sink is then the bits of -inf: the unsinked row), and stores one fp32 per row in the epilogue. Translation units
+// of its own once more.
+#ifndef FA_W4_LSE
+#define FA_W4_LSE 0
+#endif
+#if FA_W4_LSE && !FA_W4_SINK
+#error "FA_W4_LSE needs FA_W4_SINK"
+#endif
+#if FA_W4_LSE
+// w4_sink_inv (its tokens, so O's factor keeps its bits) that also hands out the BITS of the row's natural-log
+// LSE, ln(sum_n exp(s_n) + exp(sink)) = (Ms + log2 L') ln 2, from the same Ms and L'. A row without a visible key
+// (L == 0) has the sink alone: its clamped value where the head has one (above kNeg), else -inf -- by its bits under
+// an explicit compare, since the build is -ffinite-math-only and (M + log2 0) ln 2 is nothing to rely on; the clamped
+// "no sink" of about -1e30 never reaches the result.
+// (a constant materialised HERE, in a VGPR: hoisted out of the persistent block loop, the epilogue's constants were
+// live across the whole kernel, and in one instantiation hipcc parked them in the O AGPRs)
+__device__ __forceinline__ uint32_t w4_const_here(uint32_t x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ float w4_sink_inv_lse(const uint32_t sink_bits, const float M, const float L,
+                                                 uint32_t &lse_bits) {
+#pragma clang fp contract(off)
+    const uint32_t mag = min(sink_bits & 0x7fffffffu, __float_as_uint(-kNeg));
+    float sink = __uint_as_float(mag | (sink_bits & 0x80000000u));
+    pin(sink);
+    const float s2 = sink * 1.4426950408889634f;
+    const float Ms = fmaxf(M, s2);
+    const float e = __builtin_amdgcn_exp2f(M - Ms);
+    const float Ls = __builtin_fmaf(L, e, __builtin_amdgcn_exp2f(s2 - Ms));
+    const float lse = (Ms + __builtin_amdgcn_logf(Ls)) * 0.6931471805599453f;
+    const uint32_t alone = sink > kNeg ? __float_as_uint(sink) : w4_const_here(0xff800000u);
+    lse_bits = (L == 0.f) ? alone : __float_as_uint(lse);
+    return (L == 0.f) ? 1.f : e * (1.f / Ls);
+}
+#endif
 #if FA_W4_PAGED
 // Where the K / V tiles of one Q block of sequence b live. A page holds tpp whole 64-key tiles, so tile t is
 // tile t % tpp of page row[t / tpp]. The pipelined loop issues K tile j + 1 and V tile j in iteration j --
@@ -1009,7 +1047,14 @@ struct PagedTiles {
 // has been drained.
 // =============================================================================================
 template <class DT, bool kCausal, int kD, bool kExactD>
-#if FA_W4_SINK  // (the same name once more: the overload the sinked ragged translation units hold)
+#if FA_W4_LSE  // (and once more: the overload the translation units that also write the LSE hold)
+__global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
+                                                          unsigned long long *stamps, const PathArgs xa,
+                                                          const PagedVarlenLseArgs pl) {
+    const PagedVarlenSinkArgs ps = pl.sink;
+    const PagedPrefillArgs pg = ps.varlen.paged;
+    const int total_q = ps.varlen.total_q;
+#elif FA_W4_SINK  // (the same name once more: the overload the sinked ragged translation units hold)
 __global__ __launch_bounds__(256, 1) void fa_fwd_w4_paged(const fa_fwd_params p, const int n_qtiles, const int dbg,
                                                           unsigned long long *stamps, const PathArgs xa,
                                                           const PagedVarlenSinkArgs ps) {
@@ -1056,6 +1101,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     constexpr int NP = T / 4 / 1024;  // LDS-DMA pieces per wave per K or V tile (4 / 2)
     constexpr int ROWS_PER_PIECE = 1024 / RB;
     constexpr int kOStores = 2 * DTL * 2;  // O stores per wave and block (epilogue)
+#if FA_W4_LSE
+    constexpr int kLseStores = 2;  // LSE stores per wave and block (epilogue): one per 32-row block, issued by
+                                   // every wave of every block, so the prologue's counted wait stays exact
+    static_assert(kOStores + kLseStores < 64, "the counted wait is a 6-bit vmcnt");
+#endif
 #ifdef FA_V0
     constexpr int kV0 = FA_V0;
 #else
@@ -1291,6 +1341,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
 #if FA_W4_SINK
     uint32_t sink_u = 0;  // (set_block: the bits of sinks[this block's q-head], wave-uniform)
 #endif
+#if FA_W4_LSE
+    int lse_hq = 0, lse_q0 = 0;  // (set_block: this block's q-head and its sequence's first packed row, in SGPRs:
+                                 // as a pointer in VGPRs they were live across the key loop, and at D = 128 hipcc
+                                 // spilled into the O AGPRs)
+#endif
     auto q_rows_of = [&](const int b, int &q0) __attribute__((always_inline)) {
         const int bu = __builtin_amdgcn_readfirstlane(b);
         q0 = min(max(xa.q_rng[bu], 0), total_q);
@@ -1309,12 +1364,21 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
             Sq = q_rows_of(b, q0);
             qrow0 = (int64_t)q0 * p.q_seqlen_stride;
             orow0 = (int64_t)q0 * p.o_seqlen_stride;
+#if FA_W4_LSE
+            lse_hq = __builtin_amdgcn_readfirstlane(hq);
+            lse_q0 = __builtin_amdgcn_readfirstlane(q0);
+#endif
         }
 #if FA_W4_SINK
         // this block's sink: one q-head per block, so one value per wave. A scalar load through the constant
         // space, here, where the block's q-head is decoded -- a vector load in the epilogue would sit inside the
         // next prologue's counted vmcnt(kOStores), and its result would force a vmcnt(0) on the next block's DMA
+#if FA_W4_LSE  // (sinks may be NULL here: every head then has the bits of -inf, a wave-uniform select)
+        sink_u = ps.sinks ? ((const __attribute__((address_space(4))) uint32_t *)ps.sinks)[__builtin_amdgcn_readfirstlane(hq)]
+                          : 0xff800000u;
+#else
         sink_u = ((const __attribute__((address_space(4))) uint32_t *)ps.sinks)[__builtin_amdgcn_readfirstlane(hq)];
+#endif
 #endif
 #else
         if (xa.q_rng) {  // this batch row's query rows and keys: absolute rows (the host zeroes the
@@ -1416,7 +1480,13 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
     // into VGPRs, rotate-half in fp32, rounded once to T, then into the Q AGPRs. The rotation partner
     // of chunk 2ks+h is chunk 2(ks +- KS/2)+h -- the same lane. Issued in the block prologue (not
     // under the previous block's drain, whose S / P registers are live) and waited for there.
+#if FA_W4_LSE
+    // (this launch never carries RoPE tables, launch_prefill_paged_varlen_lse: compiled out here, the dead
+    // load_q_rope was where hipcc, two SGPRs and a few epilogue VGPRs further on, parked a VGPR in the O AGPRs)
+    constexpr bool rope_q = false;
+#else
     const bool rope_q = kExactD && xa.cos != nullptr;
+#endif
     auto load_q_rope = [&]() __attribute__((always_inline)) {
         const int qs = (int)p.q_seqlen_stride, cs = (int)xa.seq_stride;
         const int rows = min(Sq - mw, rowB + 32);
@@ -2079,7 +2149,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
 #ifdef FA_STAMPS
     const uint32_t st_w0 = (uint32_t)__builtin_amdgcn_s_memtime();
 #endif
+#if FA_W4_LSE  // (the previous block left its O stores AND its LSE stores behind these loads)
+    if (rnd == 0) dma_wait(); else __builtin_amdgcn_s_waitcnt(vmcnt_enc(kOStores + kLseStores));
+#else
     if (rnd == 0 || (FA_EPI_OVL && !spl)) dma_wait(); else __builtin_amdgcn_s_waitcnt(vmcnt_enc(kOStores));
+#endif
 #ifdef FA_STAMPS
     st_acc[6] = (uint32_t)__builtin_amdgcn_s_memtime() - st_w0;  // (the wait for this block's Q and K_0)
 #endif
@@ -2362,6 +2436,9 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
 #if FA_W4_SINK
     const uint32_t sink_c = sink_u;  // (set_block below loads the NEXT block's)
 #endif
+#if FA_W4_LSE
+    const int lse_hq_c = lse_hq, lse_q0_c = lse_q0;
+#endif
 #ifdef FA_STAMPS
     const uint32_t blk_c = xcd + 8 * kblk;
 #endif
@@ -2529,8 +2606,14 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
 #if FA_EPI_OVL
 #error "FA_W4_SINK: the deferred epilogue (FA_EPI_OVL) takes row sums, not factors"
 #endif
+#if FA_W4_LSE
+        uint32_t lse0, lse1;  // (the bits of the two rows' LSE, from w4_sink_inv's own Ms and L')
+        const float l0 = w4_sink_inv_lse(sink_c, -st[0].nmsc, pair_sum(st[0].l), lse0);
+        const float l1 = w4_sink_inv_lse(sink_c, -st[1].nmsc, pair_sum(st[1].l), lse1);
+#else
         const float l0 = w4_sink_inv(sink_c, -st[0].nmsc, pair_sum(st[0].l));
         const float l1 = w4_sink_inv(sink_c, -st[1].nmsc, pair_sum(st[1].l));
+#endif
 #else
         const float l0 = pair_sum(st[0].l);
         const float l1 = pair_sum(st[1].l);
@@ -2547,8 +2630,32 @@ __global__ __launch_bounds__(256, 1) void fa_fwd_w4(const fa_fwd_params p, const
         {
             store_block(r, IC<0>{}, l0);
             store_block(r + rowb_c, IC<16 * DTL>{}, l1);
+#if FA_W4_LSE
+            // the two rows' LSE: one fp32 each at lb_c + 4 * (row of the wave's slab) * lse_row_stride, through a descriptor
+            // that ends with the sequence's last row of this wave's slab (orr's row bound). Both lane halves hold
+            // the same row, so the upper half's offset goes out of range, and so does a row at or past Sq_b (an
+            // explicit compare: with a row stride of 0 the descriptor's bound alone would let it through). Selects,
+            // no branches: every wave issues exactly kLseStores more stores per block, as the counted wait of the
+            // next block's prologue assumes.
+            const int lrows = min(sq_c - mw_c, rowb_c + 32), lrs = (int)pl.lse_row_stride;
+            const char *const lb_c = (const char *)pl.lse + 4 * ((int64_t)lse_hq_c * pl.lse_head_stride +
+                                                                 (int64_t)(lse_q0_c + mw_c) * pl.lse_row_stride);
+            const rsrc_t lrr = make_rsrc_u(lb_c, lrows <= 0 ? 0u : (uint32_t)(((lrows - 1) * lrs + 1) * 4));
+            // (the two stores are ONE asm statement: through the builtin hipcc turned the selects into divergent
+            // branches with a copy of the first store in each arm, three instructions for two stores. 5 wait
+            // states ahead of them: the descriptor may come from a VALU write of SGPRs, as in dma_q)
+            const int lrow1 = r + rowb_c;
+            const uint32_t lnone = w4_const_here(0x7ffffff0u);
+            const uint32_t loff0 = ((h == 0) & (r < lrows)) ? (uint32_t)(r * lrs * 4) : lnone;
+            const uint32_t loff1 = ((h == 0) & (lrow1 < lrows)) ? (uint32_t)(lrow1 * lrs * 4) : lnone;
+            asm volatile("s_nop 4\n\tbuffer_store_dword %0, %1, %4, 0 offen\n\tbuffer_store_dword %2, %3, %4, 0 offen"
+                         :: "v"(lse0), "v"(loff0), "v"(lse1), "v"(loff1), "s"(lrr) : "memory");
+#endif
         }
     } else {
+#if FA_W4_LSE
+        static_assert(!spl, "FA_W4_LSE: a key-split piece's combine would store final rows without their LSE");
+#endif
         // ---- key-split block: the two pieces meet per wave. The first to arrive leaves its
         // unnormalised O (AGPR fragment order, 64 lanes x 16 B per record) and its (nmsc, l, m) per
         // lane in the workspace and marks them ready in the arrivals word; the second finds them

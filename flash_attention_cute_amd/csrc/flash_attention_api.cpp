@@ -36,6 +36,7 @@
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
+#include "fa_gfx950_paged_varlen_lse.h"
 #include "fa_gfx950_paged_varlen_sink.h"
 #include "fa_gfx950_paged_window.h"
 #include "fa_gfx950_sink.h"
@@ -1000,8 +1001,10 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_lse_fwd(
 // Merge of partial attention states (include/fa_gfx950_lse.h fa_merge_states_gfx950): outs [N, B, H, S, D]
 // fp16 / bf16 and lses [N, B, H, S] fp32 (any strides; outs copied only if not 16-byte aligned) -> (out
 // [B, H, S, D], lse [B, H, S] or an empty tensor). One HIP pass.
-std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states(torch::Tensor &outs, torch::Tensor &lses,
-                                                                      bool return_lse) {
+// merge_states_into: the checks and the launch, into `o` [B, H, S, D] and `lse` [B, H, S] (undefined: none) as the
+// caller laid them out -- views of any strides the library takes (the packed merge passes transposed ones).
+void merge_states_into(const torch::Tensor &outs, const torch::Tensor &lses, torch::Tensor &o, torch::Tensor &lse) {
+    const bool return_lse = lse.defined();
     TORCH_CHECK(outs.dim() == 5 && lses.dim() == 4, "outs must be [parts, batch, heads, seqlen, dim], lses "
                 "[parts, batch, heads, seqlen]");
     TORCH_CHECK(outs.sizes().slice(0, 4) == lses.sizes(), "outs and lses must agree in their first four dimensions");
@@ -1019,8 +1022,6 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states(torch::Ten
     bool lok = true;
     for (int i = 0; i < 4; ++i) lok = lok && (lses.size(i) == 1 || lses.stride(i) >= 0);
     torch::Tensor lx = lok ? lses : lses.contiguous();
-    auto o = torch::empty({ox.size(1), ox.size(2), ox.size(3), ox.size(4)}, ox.options());
-    torch::Tensor lse = return_lse ? torch::empty({ox.size(1), ox.size(2), ox.size(3)}, lx.options()) : torch::Tensor();
     fa_merge_params mp;
     memset(&mp, 0, sizeof(mp));
     mp.outs = ox.data_ptr();
@@ -1050,7 +1051,16 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states(torch::Ten
     }
     check_rc(fa_merge_states_gfx950(&mp, ox.dtype() == torch::kHalf ? FA_DTYPE_F16 : FA_DTYPE_BF16, current_stream(ox)),
              "fa_merge_states_gfx950");
-    return {o, return_lse ? lse : torch::empty({0}, lx.options())};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states(torch::Tensor &outs, torch::Tensor &lses,
+                                                                      bool return_lse) {
+    TORCH_CHECK(outs.dim() == 5 && lses.dim() == 4, "outs must be [parts, batch, heads, seqlen, dim], lses "
+                "[parts, batch, heads, seqlen]");
+    auto o = torch::empty({outs.size(1), outs.size(2), outs.size(3), outs.size(4)}, outs.options());
+    torch::Tensor lse = return_lse ? torch::empty({outs.size(1), outs.size(2), outs.size(3)}, lses.options()) : torch::Tensor();
+    merge_states_into(outs, lses, o, lse);
+    return {o, return_lse ? lse : torch::empty({0}, lses.options())};
 }
 
 // In-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache.h fa_kvcache_append_gfx950): the new
@@ -1213,11 +1223,33 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_fp8(
 //
 // sinks (flash_attention_paged_varlen_sink_fwd, include/fa_gfx950_paged_varlen_sink.h): fp32 [Hq] on q's device, one
 // extra softmax column per q-head of that logit and value 0; the same steps, the sink entry.
+//
+// with_lse (flash_attention_paged_varlen_lse_fwd, include/fa_gfx950_paged_varlen_lse.h): the launch also writes the
+// natural-log LSE of every owned row, fp32 [Hq, total_q]; sinks may then be absent. `out` and `lse` of the struct are
+// the destinations where the caller brought them (the two states of a shared-prefix step are written side by side
+// into one stacked tensor, so their merge needs no copy), else allocated here; both hold the results afterwards.
+struct RaggedLse {
+    torch::Tensor out, lse;
+};
 torch::Tensor paged_varlen_impl(torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache,
                                 torch::Tensor &cu_seqlens_q, int64_t max_seqlen_q, torch::Tensor &block_table,
                                 torch::Tensor &cache_seqlens, int64_t window_left, float softmax_scale, bool causal,
-                                const torch::Tensor *sinks = nullptr) {
+                                const torch::Tensor *sinks = nullptr, RaggedLse *with_lse = nullptr) {
     TORCH_CHECK(q.dim() == 3, "ragged q must be 3-D [total_q, heads, dim]");
+    if (with_lse && with_lse->out.defined()) {
+        const torch::Tensor &d = with_lse->out;
+        TORCH_CHECK(d.sizes() == q.sizes() && d.dtype() == q.dtype() && d.device() == q.device(),
+                    "out must have the shape, dtype and device of q");
+        TORCH_CHECK(d.stride(2) == 1 && aligned_rows(d),
+                    "out must have contiguous rows, strides that are multiples of 8 and a 16-byte aligned base");
+    }
+    if (with_lse && with_lse->lse.defined()) {
+        const torch::Tensor &d = with_lse->lse;
+        TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(1) && d.size(1) == q.size(0) && d.dtype() == torch::kFloat32 &&
+                        d.device() == q.device(),
+                    "lse must be fp32 [heads of q, total_q] on the device of q");
+        TORCH_CHECK(d.stride(0) >= 0 && d.stride(1) >= 0, "lse must have non-negative strides");
+    }
     torch::Tensor sinks_c;
     if (sinks) {
         TORCH_CHECK(sinks->dim() == 1 && sinks->size(0) == q.size(1) && sinks->dtype() == torch::kFloat32,
@@ -1243,11 +1275,17 @@ torch::Tensor paged_varlen_impl(torch::Tensor &q, torch::Tensor &k_cache, torch:
     c10::DeviceGuard device_guard(q.device());
     require_gfx950(q.device());
 
-    auto o = torch::empty_like(q);
+    auto o = with_lse && with_lse->out.defined() ? with_lse->out : torch::empty_like(q);
+    if (with_lse) {
+        if (!with_lse->lse.defined())
+            with_lse->lse = torch::empty({q.size(1), q.size(0)}, q.options().dtype(torch::kFloat32));
+        with_lse->out = o;
+    }
     // nothing to launch: no row, no q-tile, or an empty step (batch 0, as the append and the C ABI take it)
     if (q.size(0) == 0 || max_seqlen_q == 0 || bs == 0) return o;
     torch::Tensor qx = aligned_rows(q) ? q : q.contiguous();
     if (!aligned_rows(o) || o.stride(2) != 1) o = torch::empty(q.sizes(), q.options());
+    if (with_lse) with_lse->out = o;
     torch::Tensor cq = cu_seqlens_q.contiguous();
 
     fa_paged_varlen_params vp;
@@ -1267,6 +1305,29 @@ torch::Tensor paged_varlen_impl(torch::Tensor &q, torch::Tensor &k_cache, torch:
     vp.cu_seqlens_q = cq.data_ptr<int32_t>();
     vp.total_q = qx.size(0);
     const int dtype = fa_dtype(qx), c = causal ? 1 : 0;
+    if (with_lse) {
+        fa_paged_varlen_lse_params lp;
+        memset(&lp, 0, sizeof(lp));
+        lp.varlen = vp;
+        lp.sinks = sinks ? sinks_c.data_ptr<float>() : nullptr;
+        // (fill_lse on the [1, Hq, total_q] view: its head and row strides are this entry's two)
+        struct {
+            float *lse_ptr;
+            int64_t lse_batch_stride, lse_head_stride, lse_seqlen_stride, seqlen_offset;
+        } dst;
+        fill_lse(dst, with_lse->lse.unsqueeze(0), 0);
+        lp.lse_ptr = dst.lse_ptr;
+        lp.lse_head_stride = dst.lse_head_stride;
+        lp.lse_row_stride = dst.lse_seqlen_stride;
+        launch_with_workspace(
+            "fa_fwd_gfx950_paged_varlen_lse",
+            [&] { return fa_fwd_gfx950_paged_varlen_lse_workspace_size(&lp, dtype, c, window_left); },
+            [&](void *ws, int64_t ws_bytes) {
+                return fa_fwd_gfx950_paged_varlen_lse(&lp, dtype, c, window_left, ws, ws_bytes, current_stream(qx));
+            },
+            qx.options());
+        return o;
+    }
     if (sinks) {
         fa_paged_varlen_sink_params sp;
         memset(&sp, 0, sizeof(sp));
@@ -1308,6 +1369,37 @@ torch::Tensor flash_attention_paged_varlen_sink_fwd(torch::Tensor &q, torch::Ten
                                                     bool causal) {
     return paged_varlen_impl(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens, window_left,
                              softmax_scale, causal, &sinks);
+}
+
+// The same that also returns the LSE (include/fa_gfx950_paged_varlen_lse.h fa_fwd_gfx950_paged_varlen_lse): sinks
+// optional; (out [total_q, Hq, D], lse fp32 [Hq, total_q], natural log). out_dst / lse_dst: written in place and
+// returned when given (views into a stacked pair of states), else allocated.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_paged_varlen_lse_fwd(
+    torch::Tensor &q, torch::Tensor &k_cache, torch::Tensor &v_cache, torch::Tensor &cu_seqlens_q,
+    int64_t max_seqlen_q, torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+    c10::optional<torch::Tensor> sinks, int64_t window_left, float softmax_scale, bool causal,
+    c10::optional<torch::Tensor> out_dst, c10::optional<torch::Tensor> lse_dst) {
+    RaggedLse r{out_dst.has_value() ? *out_dst : torch::Tensor(), lse_dst.has_value() ? *lse_dst : torch::Tensor()};
+    paged_varlen_impl(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens, window_left,
+                      softmax_scale, causal, sinks.has_value() ? &*sinks : nullptr, &r);
+    return {r.out, r.lse};
+}
+
+// Merge of PACKED partial states, the layout of the ragged step (fa_merge_states_gfx950 with B = 1, Sq = total_q: it
+// takes every stride this needs): outs [N, total_q, H, D], lses [N, H, total_q] -> (out [total_q, H, D] contiguous,
+// lse [H, total_q] or an empty tensor). One HIP pass, as flash_attention_merge_states.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_merge_states_packed(torch::Tensor &outs, torch::Tensor &lses,
+                                                                             bool return_lse) {
+    TORCH_CHECK(outs.dim() == 4 && lses.dim() == 3, "packed outs must be [parts, total_q, heads, dim], lses "
+                "[parts, heads, total_q]");
+    TORCH_CHECK(outs.size(0) == lses.size(0) && outs.size(1) == lses.size(2) && outs.size(2) == lses.size(1),
+                "packed outs [parts, total_q, heads, dim] and lses [parts, heads, total_q] must agree");
+    torch::Tensor o = torch::empty({outs.size(1), outs.size(2), outs.size(3)}, outs.options());
+    torch::Tensor lse = return_lse ? torch::empty({lses.size(1), lses.size(2)}, lses.options()) : torch::Tensor();
+    torch::Tensor outs5 = outs.unsqueeze(1).transpose(2, 3), lses4 = lses.unsqueeze(1);
+    torch::Tensor o4 = o.unsqueeze(0).transpose(1, 2), lse3 = return_lse ? lse.unsqueeze(0) : torch::Tensor();
+    merge_states_into(outs5, lses4, o4, lse3);
+    return {o, return_lse ? lse : torch::empty({0}, lses.options())};
 }
 
 // Ragged in-place KV-cache append with fused RoPE (include/fa_gfx950_kvcache_varlen.h
@@ -1459,4 +1551,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_paged_varlen_sink_fwd", &flash_attention::flash_attention_paged_varlen_sink_fwd,
           "Ragged query blocks over a 16-bit paged KV cache with attention sinks, windowed or not, gfx950");
     m.def("paged_varlen_sink_version", []() { return fa_paged_varlen_sink_version(); });
+    m.def("flash_attention_paged_varlen_lse_fwd", &flash_attention::flash_attention_paged_varlen_lse_fwd,
+          "Ragged query blocks over a 16-bit paged KV cache, returning (out, lse); sinks and window optional, gfx950");
+    m.def("paged_varlen_lse_version", []() { return fa_paged_varlen_lse_version(); });
+    m.def("flash_attention_merge_states_packed", &flash_attention::flash_attention_merge_states_packed,
+          "Merge packed partial attention states ([N, total_q, H, D], lse [N, H, total_q]), one HIP pass (gfx950)");
 }

@@ -1338,6 +1338,29 @@ def flash_attention_merge_states_fake(outs, lses, return_lse=False):
             lses.new_empty(lses.shape[1:]) if return_lse else lses.new_empty(0))
 
 
+# The merge of PACKED states (outs [N, total_q, H, D], lses [N, H, total_q] -> out [total_q, H, D], lse [H, total_q]):
+# an op beside merge_states, which allocates [B, H, S, D] and keeps its schema; the same kernel and C entry.
+@torch.library.custom_op("flash_attention::merge_states_packed", mutates_args=())
+def flash_attention_merge_states_packed(outs: torch.Tensor, lses: torch.Tensor,
+                                        return_lse: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    o, lse = _merge_reference(outs.transpose(1, 2), lses, return_lse)  # ([N, H, T, D] against [N, H, T])
+    return o.transpose(0, 1).contiguous(), lse
+
+
+@torch.library.register_kernel("flash_attention::merge_states_packed", "cuda")
+def flash_attention_merge_states_packed_cuda(outs: torch.Tensor, lses: torch.Tensor,
+                                             return_lse: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_merge_states_packed(outs, lses, return_lse)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::merge_states_packed")
+def flash_attention_merge_states_packed_fake(outs, lses, return_lse=False):
+    return (outs.new_empty(outs.shape[1:]),
+            lses.new_empty(lses.shape[1:]) if return_lse else lses.new_empty(0))
+
+
 def flash_attn_merge_states(outs, lses, return_lse=False):
     """Merge N partial attention states over DISJOINT key sets: ``outs`` [N, B, Hq, Sq, D] (fp16 / bf16, D a
     multiple of 8) and ``lses`` [N, B, Hq, Sq] (fp32, natural log, as ``flash_attn_paged_func(return_lse=True)``
@@ -1345,20 +1368,33 @@ def flash_attn_merge_states(outs, lses, return_lse=False):
     ``w_i = exp(lse_i - max_i lse_i)``, ``out = sum_i w_i o_i / sum_i w_i`` in fp32 rounded once, ``lse = max_i lse_i
     + ln sum_i w_i``; a part with ``lse = -inf`` weighs 0 and a row whose parts all are gives 0 and ``-inf``.
     1 <= N <= 16. One memory-bound HIP pass, no host synchronisation (graph-capturable). Returns ``out`` or
-    ``(out, lse)``."""
+    ``(out, lse)``.
+
+    PACKED states, the layout of the ragged step (``flash_attn_paged_varlen_func(return_lse=True)``): ``outs``
+    [N, total_q, Hq, D] with ``lses`` [N, Hq, total_q], or sequences of N such tensors; returns ``out``
+    [total_q, Hq, D] contiguous and ``lse`` [Hq, total_q]. The same kernel and rule (one batch row of ``total_q``
+    positions, read through the packed strides)."""
     if not isinstance(outs, torch.Tensor):
         outs = torch.stack(list(outs))
     if not isinstance(lses, torch.Tensor):
         lses = torch.stack(list(lses))
-    if outs.dim() != 5 or lses.dim() != 4 or outs.shape[:4] != lses.shape:
+    packed = outs.dim() == 4 and lses.dim() == 3
+    if packed:
+        if outs.size(0) != lses.size(0) or outs.size(1) != lses.size(2) or outs.size(2) != lses.size(1):
+            raise ValueError(f"packed outs must be [N, total_q, Hq, D] and lses [N, Hq, total_q] (got "
+                             f"{tuple(outs.shape)} and {tuple(lses.shape)})")
+    elif outs.dim() != 5 or lses.dim() != 4 or outs.shape[:4] != lses.shape:
         raise ValueError(f"outs must be [N, B, Hq, Sq, D] and lses [N, B, Hq, Sq] (got {tuple(outs.shape)} and "
                          f"{tuple(lses.shape)})")
     if not 1 <= outs.size(0) <= 16:
         raise ValueError(f"1 to 16 partial states can be merged (got {outs.size(0)})")
-    if outs.size(4) % 8 != 0:
-        raise ValueError(f"the head dim must be a multiple of 8 (got {outs.size(4)})")
+    if outs.size(-1) % 8 != 0:
+        raise ValueError(f"the head dim must be a multiple of 8 (got {outs.size(-1)})")
     if lses.dtype != torch.float32:
         raise ValueError(f"lses must be fp32 (got {lses.dtype})")
+    if packed:
+        o, lse = torch.ops.flash_attention.merge_states_packed(outs, lses, return_lse)
+        return (o, lse) if return_lse else o
     o, lse = torch.ops.flash_attention.merge_states(outs, lses, return_lse)
     return (o, lse) if return_lse else o
 
@@ -1515,17 +1551,29 @@ def _paged_varlen_unsupported(q, k_cache, v_cache):
 
 
 def _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cache_seqlens, softmax_scale, causal,
-                            window_left, sinks=None):
+                            window_left, sinks=None, return_lse=False):
     """The non-GPU default of the ragged paged ops: a per-sequence loop in the style of ``_paged_reference`` (the
     sequence's pages gathered, torch SDPA under the kernel's masks, rows with no visible key 0, both arrays clamped
-    as the kernel clamps them). ``sinks`` (the sink op): one extra softmax column per q-head."""
+    as the kernel clamps them). ``sinks`` (the sink op): one extra softmax column per q-head. ``return_lse`` (the
+    LSE op): also the float LSE [Hq, total_q], ``ln(sum_n exp(s_n) + exp(sinks[h]))`` over the row's visible keys --
+    a sink at or below -1e30 adds nothing, an owned row with no visible key has its sink (``-inf`` without one), a
+    row that no sequence owns ``-inf``."""
     window_left = min(int(window_left), _MAX_WINDOW)
     out = torch.zeros_like(q)
+    if return_lse:
+        lse = torch.full((q.size(1), q.size(0)), float("-inf"), dtype=torch.float32, device=q.device)
+        sink_col = None
+        if sinks is not None:
+            sink_col = sinks.float().masked_fill(sinks.float() <= -1e30, float("-inf")).clamp(max=1e30)[:, None]
+        scale = q.size(-1) ** -0.5 if softmax_scale is None else softmax_scale
+        g = q.size(1) // k_cache.size(1)
     num_pages, _, page_size, _ = k_cache.shape
     cap = block_table.size(1) * page_size
     lens = cache_seqlens.tolist()
     for b, (q0, q1) in enumerate(_clamped_ranges(cu_seqlens_q, q.size(0))):
         n, sq = min(max(lens[b], 0), cap), q1 - q0
+        if return_lse and sink_col is not None:
+            lse[:, q0:q1] = sink_col
         if n == 0 or sq == 0:
             continue
         first = max(0, n - sq - window_left) // page_size if window_left >= 0 else 0  # the first page read
@@ -1542,7 +1590,13 @@ def _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cach
             out[q0:q1] = _sdpa_with_sink(qb, kb, vb, mask, softmax_scale, sinks)[0].transpose(0, 1)
         else:
             out[q0:q1] = _masked_sdpa(qb, kb, vb, mask, softmax_scale)[0].transpose(0, 1)
-    return out
+        if return_lse:
+            sc = torch.matmul(qb[0].float(), kb[0].float().repeat_interleave(g, dim=0).transpose(1, 2)) * scale
+            if mask is not None:
+                sc = sc.masked_fill(~mask[None], float("-inf"))
+            l = torch.logsumexp(sc, dim=-1)  # [Hq, sq]
+            lse[:, q0:q1] = l if sink_col is None else torch.logaddexp(l, sink_col.expand_as(l))
+    return (out, lse) if return_lse else out
 
 
 @torch.library.custom_op("flash_attention::paged_varlen_forward", mutates_args=())
@@ -1616,8 +1670,55 @@ def flash_attention_paged_varlen_forward_sink_fake(q, k_cache, v_cache, cu_seqle
     return torch.empty_like(q)
 
 
+# The same that also returns the softmax log-sum-exp (include/fa_gfx950_paged_varlen_lse.h
+# fa_fwd_gfx950_paged_varlen_lse): an op of its own once more, so that the two above keep their schemas. ``sinks``
+# is optional here (ONE kernel family: without it every head's sink is -inf); lse fp32 [Hq, total_q], natural log.
+@torch.library.custom_op("flash_attention::paged_varlen_forward_lse", mutates_args=())
+def flash_attention_paged_varlen_forward_lse(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                             cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                                             block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                             sinks: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                             causal: bool = False,
+                                             window_left: int = -1) -> tuple[torch.Tensor, torch.Tensor]:
+    # Non-GPU default: _paged_varlen_reference with the float LSE.
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    return _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, block_table, cache_seqlens, softmax_scale,
+                                   causal, window_left, sinks, return_lse=True)
+
+
+def _paged_varlen_lse_cuda(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens, sinks,
+                           softmax_scale, causal, window_left, out=None, lse=None):
+    _require_ext()
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    return flash_attention_cuda.flash_attention_paged_varlen_lse_fwd(
+        q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), block_table, cache_seqlens, sinks,
+        min(int(window_left), _MAX_WINDOW), softmax_scale, causal, out, lse)
+
+
+@torch.library.register_kernel("flash_attention::paged_varlen_forward_lse", "cuda")
+def flash_attention_paged_varlen_forward_lse_cuda(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                                                  cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                                                  block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                                  sinks: Optional[torch.Tensor] = None, softmax_scale: float = None,
+                                                  causal: bool = False,
+                                                  window_left: int = -1) -> tuple[torch.Tensor, torch.Tensor]:
+    o, lse = _paged_varlen_lse_cuda(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens,
+                                    sinks, softmax_scale, causal, window_left)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::paged_varlen_forward_lse")
+def flash_attention_paged_varlen_forward_lse_fake(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                                  cache_seqlens, sinks=None, softmax_scale=None, causal=False,
+                                                  window_left=-1):
+    return torch.empty_like(q), q.new_empty((q.shape[1], q.shape[0]), dtype=torch.float32)
+
+
 def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, cache_seqlens,
-                                 softmax_scale=None, causal=False, window_left=-1, sinks=None):
+                                 softmax_scale=None, causal=False, window_left=-1, sinks=None, return_lse=False):
     """Attention of RAGGED query blocks over a paged KV cache, in one launch: ``q`` [total_q, Hq, D] packed
     (flash-attn's varlen layout), sequence b owning rows ``[cu_seqlens_q[b], cu_seqlens_q[b + 1])`` (int32
     [B + 1] on q's device) -- its LAST ``Sq_b`` positions over ``L_b = clamp(cache_seqlens[b], 0, max_pages *
@@ -1653,7 +1754,16 @@ def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
     prompt chunk of a model with sinks goes -- a UNIFORM chunk too, with a uniform ``cu_seqlens_q``, since
     ``flash_attn_paged_func`` serves sinks for decode shapes only. ``None`` is the call without the argument, bit
     for bit. The same layouts only: with FP8 pools, other page sizes or head dims it is ``NotImplementedError``
-    as above, and those alternatives have no sinks beyond decode shapes."""
+    as above, and those alternatives have no sinks beyond decode shapes.
+
+    ``return_lse=True`` returns ``(out, lse)``: ``lse`` fp32 [Hq, total_q] contiguous (flash-attn's varlen layout),
+    ``ln(sum_n exp(s_n) + exp(sinks[h]))`` over the row's visible keys in natural-log units, with or without
+    ``sinks`` and ``window_left`` -- the partial state ``flash_attn_merge_states`` combines with the states of other
+    key sets (keys sharded over devices or pools, a shared prefix:
+    ``flash_attn_paged_varlen_shared_prefix_func``). A row without a visible key has ``lse = sinks[h]`` (the sink's
+    weight over its zero value), or ``-inf`` without a sink; pass ``sinks`` to exactly ONE of the states that are
+    merged. ``out`` has the bits of the call without ``return_lse``; rows that no sequence owns are unspecified in
+    both. ``False`` is the call without the argument, bit for bit, through the ops without the LSE."""
     softmax_scale = _default_scale(q, softmax_scale)
     if sinks is not None:
         sinks = _sinks_arg(sinks, q)
@@ -1662,6 +1772,11 @@ def flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q
         if longest > int(max_seqlen_q):
             raise ValueError(f"max_seqlen_q={int(max_seqlen_q)} is smaller than the longest sequence ({longest}) "
                              "in cu_seqlens_q")
+    if return_lse:
+        out, lse = torch.ops.flash_attention.paged_varlen_forward_lse(q, k_cache, v_cache, cu_seqlens_q,
+                                                                      int(max_seqlen_q), block_table, cache_seqlens,
+                                                                      sinks, softmax_scale, causal, int(window_left))
+        return out, lse
     if sinks is not None:
         return torch.ops.flash_attention.paged_varlen_forward_sink(q, k_cache, v_cache, cu_seqlens_q,
                                                                    int(max_seqlen_q), block_table, cache_seqlens,
@@ -1780,7 +1895,7 @@ def flash_attn_kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_new, cac
 def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, k=None, v=None,
                                    cu_seqlens_new=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                                    block_table=None, softmax_scale=None, causal=False, window_left=-1,
-                                   return_seqlens=False, sinks=None):
+                                   return_seqlens=False, sinks=None, return_lse=False):
     """One step of a continuous batch on the paged cache, ``flash_attn_with_kvcache`` in the packed layout: the
     new ``k`` / ``v`` [total_new, Hkv, D] are appended in place at ``cache_seqlens``
     (``flash_attn_kvcache_append_varlen``; ``cu_seqlens_new`` defaults to ``cu_seqlens_q``, a step's new tokens
@@ -1792,11 +1907,16 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen
 
     ``sinks`` (fp32 [Hq], or ``None``): attention sinks in the attention half, as in
     ``flash_attn_paged_varlen_func``; a bad ``sinks``, or a layout the sinked kernel does not read, is refused
-    before anything is appended."""
+    before anything is appended.
+
+    ``return_lse=True``: the attention half also returns its LSE (fp32 [Hq, total_q], as
+    ``flash_attn_paged_varlen_func(return_lse=True)``): ``(out, lse)``, or ``(out, lse, new_seqlens)`` with
+    ``return_seqlens=True``. ``False`` is the call without the argument, bit for bit."""
     if cache_seqlens is None or block_table is None:
         raise ValueError("flash_attn_varlen_with_kvcache needs cache_seqlens (int32 [batch]) and block_table")
     if sinks is not None:
         sinks = _sinks_arg(sinks, q)  # (the errors of the attention half, before anything is appended)
+    if sinks is not None or return_lse:
         _paged_varlen_unsupported(q, k_cache, v_cache)
     if (k is None) != (v is None):
         raise ValueError("k and v must be given together")
@@ -1817,6 +1937,113 @@ def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen
         else:
             new_seqlens, _ = torch.ops.flash_attention.kvcache_append_varlen(
                 k_cache, v_cache, k, v, cu_seqlens_new, cache_seqlens, block_table)
+    if return_lse:
+        out, lse = flash_attn_paged_varlen_func(q_rot, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                                new_seqlens, softmax_scale, causal, window_left, sinks, True)
+        return (out, lse, new_seqlens) if return_seqlens else (out, lse)
     out = flash_attn_paged_varlen_func(q_rot, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table, new_seqlens,
                                        softmax_scale, causal, window_left, sinks)
     return (out, new_seqlens) if return_seqlens else out
+
+
+def _varlen_lse_into(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, table, seqlens, sinks, scale, causal, out, lse):
+    """One ragged LSE launch that writes o / lse into the given tensors (as ``_lse_into`` for the decode)."""
+    if q.is_cuda:
+        _paged_varlen_lse_cuda(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, table, seqlens, sinks, scale, causal,
+                               -1, out, lse)
+    else:
+        o, l = _paged_varlen_reference(q, k_cache, v_cache, cu_seqlens_q, table, seqlens, scale, causal, -1, sinks,
+                                       return_lse=True)
+        out.copy_(o)
+        lse.copy_(l)
+
+
+def flash_attn_paged_varlen_shared_prefix_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                               cache_seqlens, prefix_len, group_size=None, softmax_scale=None,
+                                               causal=False, sinks=None, return_lse=False):
+    """One step of ``flash_attn_paged_varlen_func`` for a ragged batch whose sequences SHARE their first
+    ``prefix_len`` keys, ``group_size`` consecutive sequences at a time (``None``: the whole batch; the last group
+    may be shorter): speculative-token blocks, short chunks or parallel samples behind one system prompt. The shared
+    pages are streamed once per GROUP and q-head instead of once per sequence and q-head, and the group's rows fill
+    the kernel's 256-row blocks that a short sequence alone leaves almost empty.
+
+    The caller's contract:
+
+    * ``prefix_len`` is a Python int and a multiple of ``page_size`` (``ValueError`` otherwise), at most the
+      table's capacity;
+    * every sequence holds at least ``prefix_len + Sq_b`` keys, so its chunk lies wholly behind the prefix (a
+      sequence that does not is computed as if it did: its prefix rows are not masked);
+    * the rows of one group carry the same page ids in their first ``prefix_len / page_size`` table entries;
+      ``FA_CHECK_SHARED_PREFIX=1`` (read per call, eager only, off by default) verifies that with one host read
+      and raises ``ValueError``;
+    * no ``window_left``: a row's window would cut into the prefix per sequence (not built).
+
+    How it runs: the packed layout makes a group of sequences ONE ragged sequence whose ``cu_seqlens_q`` entries
+    are the group's boundaries. Prefix phase, one launch of the LSE kernel: ``cu_seqlens_q[0:B:c]`` and the last
+    entry, the table ``block_table[::c, :prefix_len / page_size]`` (a strided view), every group ``prefix_len``
+    keys (the lengths are the first entries of ``cache_seqlens``, which the table's capacity clamps to exactly
+    ``prefix_len``), NON-causal, ``max_seqlen_q`` times ``c``, no sinks. Suffix phase, one launch: the table
+    ``block_table[:, prefix_len / page_size:]`` with ``cache_seqlens - prefix_len`` keys, ``causal`` and ``sinks``
+    as given -- the sink is in exactly one state, which makes the merge exact. Then the packed
+    ``flash_attn_merge_states``. Three launches and two small device ops (the group boundaries, the suffix
+    lengths); no host synchronisation, so the step can be captured in a graph.
+
+    What is never read: the prefix table entries of every row but a group's first.
+
+    The result differs from ``flash_attn_paged_varlen_func`` on the same tables by rounding only (the two partial
+    outputs are rounded to q's dtype before the merge). ``prefix_len == 0`` IS ``flash_attn_paged_varlen_func``,
+    bit for bit. Returns ``out`` [total_q, Hq, D], or ``(out, lse)`` with the merged LSE [Hq, total_q]. It is an
+    explicit call: nothing dispatches to it. Measured crossover against the one-launch call: not measured."""
+    prefix_len = int(prefix_len)
+    page_size = k_cache.size(2)
+    if prefix_len < 0 or prefix_len % page_size != 0:
+        raise ValueError(f"prefix_len ({prefix_len}) must be a non-negative multiple of page_size ({page_size})")
+    if q.dim() != 3:
+        raise ValueError(f"ragged q must be [total_q, Hq, D] (got {tuple(q.shape)})")
+    b = cu_seqlens_q.numel() - 1
+    c = b if group_size is None else int(group_size)
+    if group_size is not None and c < 1:
+        raise ValueError(f"group_size ({c}) must be at least 1")
+    if prefix_len == 0:
+        return flash_attn_paged_varlen_func(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, block_table,
+                                            cache_seqlens, softmax_scale, causal, -1, sinks, return_lse)
+    n_pre = prefix_len // page_size
+    if n_pre > block_table.size(1):
+        raise ValueError(f"prefix_len ({prefix_len}) exceeds the block table's capacity "
+                         f"({block_table.size(1) * page_size})")
+    if block_table.dim() != 2 or block_table.size(0) != b or cache_seqlens.numel() != b:
+        raise ValueError(f"block_table must have, and cache_seqlens be, one row per sequence ({b})")
+    softmax_scale = _default_scale(q, softmax_scale)
+    if sinks is not None:
+        sinks = _sinks_arg(sinks, q)
+    _paged_varlen_unsupported(q, k_cache, v_cache)
+    total_q, hq, d = q.shape
+    if b <= 0 or total_q == 0:
+        out = torch.empty_like(q)
+        return (out, q.new_empty((hq, total_q), dtype=torch.float32)) if return_lse else out
+    c = min(max(c, 1), b)
+    n_groups = (b + c - 1) // c
+    if _check_shared_prefix_enabled() and not torch.compiler.is_compiling() and not (
+            q.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check_shared_prefix_table(block_table, n_pre, [(i * c, min((i + 1) * c, b)) for i in range(n_groups)])
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if block_table.stride(1) != 1:
+        block_table = block_table.contiguous()
+
+    # the two states, side by side so that the merge reads them where the launches wrote them: [0] the prefix
+    # phase, [1] the suffix phase
+    outs = torch.empty((2, total_q, hq, d), dtype=q.dtype, device=q.device)
+    lses = torch.empty((2, hq, total_q), dtype=torch.float32, device=q.device)
+    # prefix phase: the group boundaries (one device op), each group's first table row, prefix_len keys each
+    cu_groups = cu_seqlens_q if c == 1 else torch.cat([cu_seqlens_q[0:b:c], cu_seqlens_q[b:b + 1]])
+    _varlen_lse_into(q, k_cache, v_cache, cu_groups, c * int(max_seqlen_q), block_table[::c, :n_pre],
+                     cache_seqlens[:n_groups], None, softmax_scale, False, outs[0], lses[0])
+    # suffix phase: every sequence's own keys (a table without suffix columns: 0 keys, no entry is read)
+    if n_pre < block_table.size(1):
+        table, lens = block_table[:, n_pre:], cache_seqlens - prefix_len
+    else:
+        table, lens = block_table[:, :1], torch.zeros_like(cache_seqlens)
+    _varlen_lse_into(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, table, lens, sinks, softmax_scale, causal,
+                     outs[1], lses[1])
+    return flash_attn_merge_states(outs, lses, return_lse)
