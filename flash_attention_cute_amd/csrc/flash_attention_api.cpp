@@ -33,6 +33,7 @@
 #include "fa_gfx950_kvcache.h"
 #include "fa_gfx950_kvcache_varlen.h"
 #include "fa_gfx950_lse.h"
+#include "fa_gfx950_mla.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
@@ -1498,6 +1499,86 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
     return {new_seqlens, q_rot};
 }
 
+// MLA decode over a paged latent KV cache (include/fa_gfx950_mla.h fa_mla_decode_gfx950): q [B, Hq, Sq, 576] absorbed
+// queries, kv_cache [num_pages, page_size, 576] of q's dtype (any page / row strides the library takes, read in
+// place), block_table int32 [B, max_pages], cache_seqlens int32 [B] -> (o [B, Hq, Sq, 512], lse fp32 [B, Hq, Sq],
+// natural log, -inf for rows without a visible key). num_splits: 0 the plan's, n >= 1 forced. The split workspace
+// comes from torch's caching allocator on the current stream: no host synchronisation, graph-capturable.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fwd(torch::Tensor &q, torch::Tensor &kv_cache,
+                                                                        torch::Tensor &block_table,
+                                                                        torch::Tensor &cache_seqlens,
+                                                                        float softmax_scale, bool causal,
+                                                                        int64_t num_splits) {
+    TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 3,
+                "q must be 4-D [batch, heads, seqlen, 576], kv_cache 3-D [pages, page_size, 576]");
+    TORCH_CHECK(q.size(3) == 576 && kv_cache.size(2) == 576, "MLA decode is built for 576 latent columns only");
+    TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0, "q must have at least one element");
+    TORCH_CHECK(kv_cache.size(0) > 0 && kv_cache.size(1) > 0 && kv_cache.size(1) % 32 == 0,
+                "page_size must be a positive multiple of 32");
+    TORCH_CHECK(q.dtype() == kv_cache.dtype(), "q and kv_cache must have the same data type");
+    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16, "q, kv_cache only support fp16 or bf16 data type");
+    TORCH_CHECK(q.stride(3) == 1 && kv_cache.stride(2) == 1, "q, kv_cache must be contiguous in the last dimension");
+    TORCH_CHECK(num_splits >= 0, "num_splits must be non-negative");
+    TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda() && q.device() == kv_cache.device(),
+                "q, kv_cache must be on the same CUDA device");
+    const int64_t bs = q.size(0);
+    check_table(block_table, bs);
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
+                "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(block_table.device() == q.device() && cache_seqlens.device() == q.device(),
+                "block_table and cache_seqlens must be on the device of q");
+    c10::DeviceGuard device_guard(q.device());
+    require_gfx950(q.device());
+
+    torch::Tensor qx = aligned_or_contiguous(q);
+    const bool kv_ok = reinterpret_cast<uintptr_t>(kv_cache.data_ptr()) % 16 == 0 && kv_cache.stride(1) % 8 == 0 &&
+                       (kv_cache.stride(0) % 8 == 0 || kv_cache.size(0) == 1) && kv_cache.stride(0) >= 0 &&
+                       kv_cache.stride(1) >= 576;
+    torch::Tensor kvx = kv_ok ? kv_cache : kv_cache.contiguous();
+    torch::Tensor table = table_with_contiguous_rows(block_table), lens = cache_seqlens.contiguous();
+    torch::Tensor o = torch::empty({bs, q.size(1), q.size(2), 512}, q.options());
+    torch::Tensor lse = torch::empty({bs, q.size(1), q.size(2)}, q.options().dtype(torch::kFloat32));
+
+    fa_mla_params mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.q_ptr = qx.data_ptr();
+    mp.kv_ptr = kvx.data_ptr();
+    mp.o_ptr = o.data_ptr();
+    mp.lse_ptr = lse.data_ptr<float>();
+    mp.block_table = table.data_ptr<int32_t>();
+    mp.seqlens_k = lens.data_ptr<int32_t>();
+    mp.batch_size = bs;
+    mp.num_heads_q = q.size(1);
+    mp.seqlen_q = q.size(2);
+    mp.headdim_qk = 576;
+    mp.headdim_v = 512;
+    mp.q_batch_stride = stride_or_zero(qx, 0);
+    mp.q_head_stride = stride_or_zero(qx, 1);
+    mp.q_seqlen_stride = stride_or_zero(qx, 2);
+    mp.o_batch_stride = o.stride(0);
+    mp.o_head_stride = o.stride(1);
+    mp.o_seqlen_stride = o.stride(2);
+    mp.lse_batch_stride = lse.stride(0);
+    mp.lse_head_stride = lse.stride(1);
+    mp.lse_seqlen_stride = lse.stride(2);
+    mp.kv_page_stride = stride_or_zero(kvx, 0);
+    mp.kv_row_stride = kvx.stride(1);
+    mp.num_pages = kvx.size(0);
+    mp.page_size = kvx.size(1);
+    mp.max_pages = table.size(1);
+    mp.block_table_stride = table.stride(0);
+    mp.num_splits = num_splits;
+    softmax_scale *= M_LOG2E;  // (as fill_params)
+    mp.softmax_scale = softmax_scale;
+    mp.causal = causal ? 1 : 0;
+    const int dtype = fa_dtype(qx);
+    void *stream = current_stream(qx);
+    launch_with_workspace(
+        "fa_mla_decode_gfx950", [&] { return fa_mla_decode_gfx950_ws_bytes(&mp); },
+        [&](void *ws, int64_t ws_bytes) { return fa_mla_decode_gfx950(&mp, dtype, ws, ws_bytes, stream); }, qx.options());
+    return {o, lse};
+}
+
 }  // namespace flash_attention
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1556,4 +1637,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("paged_varlen_lse_version", []() { return fa_paged_varlen_lse_version(); });
     m.def("flash_attention_merge_states_packed", &flash_attention::flash_attention_merge_states_packed,
           "Merge packed partial attention states ([N, total_q, H, D], lse [N, H, total_q]), one HIP pass (gfx950)");
+    m.def("flash_attention_mla_decode_fwd", &flash_attention::flash_attention_mla_decode_fwd,
+          "MLA decode over a paged latent KV cache (576 score / 512 value columns), returning (out, lse), gfx950");
+    m.def("mla_version", []() { return fa_mla_version(); });
 }

@@ -2047,3 +2047,103 @@ def flash_attn_paged_varlen_shared_prefix_func(q, k_cache, v_cache, cu_seqlens_q
     _varlen_lse_into(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, table, lens, sinks, softmax_scale, causal,
                      outs[1], lses[1])
     return flash_attn_merge_states(outs, lses, return_lse)
+
+
+# ---------------------------------------------------------------------------------------------
+# Multi-head latent attention (MLA) decode over a paged latent KV cache (include/fa_gfx950_mla.h). No reference
+# counterpart; the decode step of DeepSeek-V2 / V3 / R1 and Kimi-K2 with absorbed queries (FlashMLA's
+# ``flash_mla_with_kvcache``): 576 score columns, the first 512 of the same rows are the value, one latent
+# stream per sequence shared by every q-head.
+# ---------------------------------------------------------------------------------------------
+_MLA_DQK, _MLA_DV = 576, 512
+
+
+def _mla_reference(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal):
+    """The non-GPU default of ``mla_decode_forward``, a float restatement: (o, lse) with the kernel's semantics
+    (lengths and page ids clamped, bottom-right causal per sequence, rows without a visible key o = 0 and
+    lse = -inf)."""
+    b_, hq, sq, _ = q.shape
+    num_pages, page_size, _ = kv_cache.shape
+    cap = block_table.size(1) * page_size
+    out = torch.zeros((b_, hq, sq, _MLA_DV), dtype=torch.float32, device=q.device)
+    lse = torch.full((b_, hq, sq), float("-inf"), dtype=torch.float32, device=q.device)
+    for b, n in enumerate(cache_seqlens.tolist()):
+        n = min(max(n, 0), cap)
+        if n == 0:
+            continue
+        ids = block_table[b, :(n + page_size - 1) // page_size].clamp(0, num_pages - 1).to(torch.int64)
+        kv = kv_cache.index_select(0, ids).float().flatten(0, 1)[:n]
+        s = torch.matmul(q[b].float(), kv.t()) * softmax_scale  # [Hq, Sq, n]
+        if causal:
+            s = s.masked_fill(~_bottom_right_causal(sq, n, q.device)[None], float("-inf"))
+        l = torch.logsumexp(s, dim=-1)
+        p = torch.exp(s - l.masked_fill(l == float("-inf"), 0)[..., None])
+        out[b], lse[b] = torch.matmul(p, kv[:, :_MLA_DV]), l
+    return out.to(q.dtype), lse
+
+
+@torch.library.custom_op("flash_attention::mla_decode_forward", mutates_args=())
+def flash_attention_mla_decode_forward(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                       cache_seqlens: torch.Tensor, softmax_scale: float, causal: bool = True,
+                                       num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    # q [B, Hq, Sq, 576], kv_cache [num_pages, page_size, 576] -> (o [B, Hq, Sq, 512], lse fp32 [B, Hq, Sq])
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _mla_reference(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal)
+
+
+@torch.library.register_kernel("flash_attention::mla_decode_forward", "cuda")
+def flash_attention_mla_decode_forward_cuda(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                            cache_seqlens: torch.Tensor, softmax_scale: float, causal: bool = True,
+                                            num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_mla_decode_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), kv_cache if kv_cache.stride(-1) == 1 else kv_cache.contiguous(),
+        block_table, cache_seqlens, softmax_scale, causal, num_splits)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::mla_decode_forward")
+def flash_attention_mla_decode_forward_fake(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal=True,
+                                            num_splits=0):
+    return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
+def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal=True, head_dim_v=512,
+                               return_lse=False, num_splits=0):
+    """MLA decode over a paged latent KV cache, one HIP kernel (plus a small combine when the keys are split).
+
+    ``q`` [B, Hq, Sq, 576] fp16 / bf16: the ABSORBED queries ``q_nope @ W_UK || q_pe`` (last stride 1).
+    ``kv_cache`` [num_pages, page_size, 576] of q's dtype, or 4-D with a singleton head axis in either position
+    (taken as a view): 512 compressed-KV columns then 64 RoPE columns per row, last stride 1, row stride a
+    multiple of 8, ``page_size % 32 == 0``. A row is the key (576 columns) and the value (its first 512).
+    ``block_table`` int32 [B, max_pages] and ``cache_seqlens`` int32 [B] as in ``flash_attn_paged_func``: page
+    ids and lengths are clamped on the device, and what a sequence does not reach is never read.
+    ``softmax_scale`` is REQUIRED (``576 ** -0.5`` is wrong for every model with this layout; DeepSeek uses
+    ``192 ** -0.5`` times its YaRN factor). ``causal``: bottom-right aligned per sequence for Sq > 1.
+
+    Returns ``out`` [B, Hq, Sq, 512] (0 for a row without a visible key), and with ``return_lse`` also ``lse``
+    fp32 [B, Hq, Sq] (natural log, -inf for such a row): the convention of ``flash_attn_paged_func(return_lse=True)``,
+    so partial states go straight into ``flash_attn_merge_states``. ``num_splits``: 0 lets the plan choose the key
+    splits, n >= 1 forces n (capped at the plan's maximum)."""
+    if softmax_scale is None:
+        raise TypeError("flash_attn_mla_decode_func needs softmax_scale: there is no default for MLA "
+                        "(the absorbed head dim 576 is not the model's scale dim)")
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise RuntimeError(f"softmax_scale must be finite and > 0 (got {softmax_scale})")
+    if head_dim_v != _MLA_DV or q.dim() != 4 or q.size(-1) != _MLA_DQK:
+        raise NotImplementedError(f"MLA decode is built for head dims (576, 512) only (got q "
+                                  f"{tuple(q.shape)}, head_dim_v {head_dim_v})")
+    if kv_cache.dim() == 4 and 1 in (kv_cache.size(1), kv_cache.size(2)):
+        kv_cache = kv_cache.squeeze(1 if kv_cache.size(1) == 1 else 2)
+    if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
+        raise ValueError(f"kv_cache must be [num_pages, page_size, 576], or 4-D with a singleton head axis "
+                         f"(got {tuple(kv_cache.shape)})")
+    if kv_cache.dtype != q.dtype:
+        raise ValueError(f"q and kv_cache must have the same data type (got {q.dtype} and {kv_cache.dtype})")
+    if kv_cache.size(1) % 32 != 0:
+        raise ValueError(f"page_size must be a multiple of 32 (got {kv_cache.size(1)})")
+    if num_splits < 0:
+        raise ValueError(f"num_splits must be non-negative (got {num_splits})")
+    o, lse = torch.ops.flash_attention.mla_decode_forward(q, kv_cache, block_table, cache_seqlens,
+                                                          float(softmax_scale), bool(causal), int(num_splits))
+    return (o, lse) if return_lse else o
