@@ -34,6 +34,7 @@
 #include "fa_gfx950_kvcache_varlen.h"
 #include "fa_gfx950_lse.h"
 #include "fa_gfx950_mla.h"
+#include "fa_gfx950_mla_fp8.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
@@ -1504,18 +1505,23 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
 // place), block_table int32 [B, max_pages], cache_seqlens int32 [B] -> (o [B, Hq, Sq, 512], lse fp32 [B, Hq, Sq],
 // natural log, -inf for rows without a visible key). num_splits: 0 the plan's, n >= 1 forced. The split workspace
 // comes from torch's caching allocator on the current stream: no host synchronisation, graph-capturable.
-std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fwd(torch::Tensor &q, torch::Tensor &kv_cache,
-                                                                        torch::Tensor &block_table,
-                                                                        torch::Tensor &cache_seqlens,
-                                                                        float softmax_scale, bool causal,
-                                                                        int64_t num_splits) {
+//
+// kv_descale non-NULL (flash_attention_mla_decode_fp8_fwd, include/fa_gfx950_mla_fp8.h fa_mla_decode_fp8_gfx950): the
+// pool is torch.float8_e4m3fn bytes (row and page strides multiples of 16), q and o stay 16-bit, *kv_descale is fp32
+// broadcastable to [B] on q's device (read on the device through its stride, 0 for a scalar) or absent for 1.0.
+std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch::Tensor &kv_cache,
+                                                         torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+                                                         float softmax_scale, bool causal, int64_t num_splits,
+                                                         const c10::optional<torch::Tensor> *kv_descale) {
+    const bool fp8 = kv_descale != nullptr;
     TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 3,
                 "q must be 4-D [batch, heads, seqlen, 576], kv_cache 3-D [pages, page_size, 576]");
     TORCH_CHECK(q.size(3) == 576 && kv_cache.size(2) == 576, "MLA decode is built for 576 latent columns only");
     TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0, "q must have at least one element");
     TORCH_CHECK(kv_cache.size(0) > 0 && kv_cache.size(1) > 0 && kv_cache.size(1) % 32 == 0,
                 "page_size must be a positive multiple of 32");
-    TORCH_CHECK(q.dtype() == kv_cache.dtype(), "q and kv_cache must have the same data type");
+    TORCH_CHECK(!fp8 || kv_cache.dtype() == torch::kFloat8_e4m3fn, "an fp8 latent cache must be torch.float8_e4m3fn");
+    TORCH_CHECK(fp8 || q.dtype() == kv_cache.dtype(), "q and kv_cache must have the same data type");
     TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16, "q, kv_cache only support fp16 or bf16 data type");
     TORCH_CHECK(q.stride(3) == 1 && kv_cache.stride(2) == 1, "q, kv_cache must be contiguous in the last dimension");
     TORCH_CHECK(num_splits >= 0, "num_splits must be non-negative");
@@ -1531,10 +1537,12 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fwd(torch::T
     require_gfx950(q.device());
 
     torch::Tensor qx = aligned_or_contiguous(q);
-    const bool kv_ok = reinterpret_cast<uintptr_t>(kv_cache.data_ptr()) % 16 == 0 && kv_cache.stride(1) % 8 == 0 &&
-                       (kv_cache.stride(0) % 8 == 0 || kv_cache.size(0) == 1) && kv_cache.stride(0) >= 0 &&
+    const int64_t kv_unit = fp8 ? 16 : 8;
+    const bool kv_ok = reinterpret_cast<uintptr_t>(kv_cache.data_ptr()) % 16 == 0 && kv_cache.stride(1) % kv_unit == 0 &&
+                       (kv_cache.stride(0) % kv_unit == 0 || kv_cache.size(0) == 1) && kv_cache.stride(0) >= 0 &&
                        kv_cache.stride(1) >= 576;
-    torch::Tensor kvx = kv_ok ? kv_cache : kv_cache.contiguous();
+    // (an fp8 pool is never copied: a layout the library does not take is its error)
+    torch::Tensor kvx = kv_ok || fp8 ? kv_cache : kv_cache.contiguous();
     torch::Tensor table = table_with_contiguous_rows(block_table), lens = cache_seqlens.contiguous();
     torch::Tensor o = torch::empty({bs, q.size(1), q.size(2), 512}, q.options());
     torch::Tensor lse = torch::empty({bs, q.size(1), q.size(2)}, q.options().dtype(torch::kFloat32));
@@ -1573,10 +1581,117 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fwd(torch::T
     mp.causal = causal ? 1 : 0;
     const int dtype = fa_dtype(qx);
     void *stream = current_stream(qx);
+    if (fp8) {
+        fa_mla_fp8_params fp;
+        memset(&fp, 0, sizeof(fp));
+        fp.base = mp;
+        torch::Tensor ds;  // (kept alive to the launch)
+        if (kv_descale->has_value()) {
+            TORCH_CHECK((*kv_descale)->dtype() == torch::kFloat32 && (*kv_descale)->device() == q.device(),
+                        "kv_descale must be an fp32 tensor on the device of q");
+            ds = (*kv_descale)->expand({bs});
+            fp.kv_descale = ds.data_ptr<float>();
+            fp.kv_descale_stride = ds.stride(0);
+        }
+        launch_with_workspace(
+            "fa_mla_decode_fp8_gfx950", [&] { return fa_mla_decode_fp8_gfx950_ws_bytes(&fp); },
+            [&](void *ws, int64_t ws_bytes) { return fa_mla_decode_fp8_gfx950(&fp, dtype, ws, ws_bytes, stream); },
+            qx.options());
+        return {o, lse};
+    }
     launch_with_workspace(
         "fa_mla_decode_gfx950", [&] { return fa_mla_decode_gfx950_ws_bytes(&mp); },
         [&](void *ws, int64_t ws_bytes) { return fa_mla_decode_gfx950(&mp, dtype, ws, ws_bytes, stream); }, qx.options());
     return {o, lse};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fwd(torch::Tensor &q, torch::Tensor &kv_cache,
+                                                                        torch::Tensor &block_table,
+                                                                        torch::Tensor &cache_seqlens,
+                                                                        float softmax_scale, bool causal,
+                                                                        int64_t num_splits) {
+    return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fp8_fwd(
+    torch::Tensor &q, torch::Tensor &kv_cache, torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+    c10::optional<torch::Tensor> kv_descale, float softmax_scale, bool causal, int64_t num_splits) {
+    return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, &kv_descale);
+}
+
+// The latent cache's write side (include/fa_gfx950_mla_fp8.h fa_mla_append_gfx950): c_kv [B, Sn, 512] and k_pe
+// [B, Sn, 64] (already rotated) of one 16-bit dtype go to rows cache_seqlens[b] .. of sequence b in kv_cache
+// [num_pages, page_size, 576], which has their dtype (the bits are copied) or is torch.float8_e4m3fn (quantized
+// with kv_descale: fp32 broadcastable to [B], or absent for 1.0). Returns new_seqlens int32 [B], a NEW tensor.
+// Inputs the kernel's 16-byte loads cannot take are copied, the cache never. No host synchronisation.
+torch::Tensor flash_attention_mla_append(torch::Tensor &kv_cache, torch::Tensor &c_kv, torch::Tensor &k_pe,
+                                         torch::Tensor &cache_seqlens, torch::Tensor &block_table,
+                                         c10::optional<torch::Tensor> kv_descale) {
+    TORCH_CHECK(kv_cache.dim() == 3 && kv_cache.size(2) == 576, "kv_cache must be [pages, page_size, 576]");
+    TORCH_CHECK(c_kv.dim() == 3 && c_kv.size(2) == 512 && k_pe.dim() == 3 && k_pe.size(2) == 64,
+                "c_kv must be [batch, new rows, 512] and k_pe [batch, new rows, 64]");
+    TORCH_CHECK(c_kv.size(0) == k_pe.size(0) && c_kv.size(1) == k_pe.size(1), "c_kv and k_pe must agree in batch and rows");
+    TORCH_CHECK(c_kv.dtype() == k_pe.dtype() && (c_kv.dtype() == torch::kHalf || c_kv.dtype() == torch::kBFloat16),
+                "c_kv and k_pe must both be fp16 or both bf16");
+    const bool fp8 = kv_cache.dtype() == torch::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8 || kv_cache.dtype() == c_kv.dtype(), "kv_cache must have the data type of c_kv or be float8_e4m3fn");
+    TORCH_CHECK(fp8 || !kv_descale.has_value(), "kv_descale goes with a float8_e4m3fn latent cache");
+    TORCH_CHECK(kv_cache.size(0) > 0 && kv_cache.size(1) > 0, "kv_cache must have at least one page and one row");
+    TORCH_CHECK(kv_cache.stride(2) == 1, "kv_cache must be contiguous in the last dimension");
+    TORCH_CHECK(kv_cache.is_cuda() && c_kv.device() == kv_cache.device() && k_pe.device() == kv_cache.device(),
+                "kv_cache, c_kv and k_pe must be on the same CUDA device");
+    const int64_t bs = c_kv.size(0), sn = c_kv.size(1);
+    check_table(block_table, bs);
+    TORCH_CHECK(cache_seqlens.dtype() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == bs,
+                "cache_seqlens must be int32 [batch]");
+    TORCH_CHECK(block_table.device() == kv_cache.device() && cache_seqlens.device() == kv_cache.device(),
+                "block_table and cache_seqlens must be on the device of kv_cache");
+    c10::DeviceGuard device_guard(kv_cache.device());
+    require_gfx950(kv_cache.device());
+    const int64_t cap = block_table.size(1) * kv_cache.size(1);
+    if (bs == 0) return cache_seqlens.clamp(0, cap);
+
+    auto rows16 = [](const torch::Tensor &t) {
+        const bool ok = t.stride(2) == 1 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                        t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(0) >= 0 && t.stride(1) >= 0;
+        return ok ? t : t.contiguous();
+    };
+    torch::Tensor ckv = rows16(c_kv), kpe = rows16(k_pe);
+    torch::Tensor table = table_with_contiguous_rows(block_table), lens = cache_seqlens.contiguous();
+    torch::Tensor new_seqlens = torch::empty({bs}, lens.options());
+
+    fa_mla_append_params p;
+    memset(&p, 0, sizeof(p));
+    p.kv_ptr = kv_cache.data_ptr();
+    p.c_kv = ckv.data_ptr();
+    p.k_pe = kpe.data_ptr();
+    p.block_table = table.data_ptr<int32_t>();
+    p.seqlens_k = lens.data_ptr<int32_t>();
+    p.seqlens_out = new_seqlens.data_ptr<int32_t>();
+    torch::Tensor ds;  // (kept alive to the launch)
+    if (kv_descale.has_value()) {
+        TORCH_CHECK(kv_descale->dtype() == torch::kFloat32 && kv_descale->device() == kv_cache.device(),
+                    "kv_descale must be an fp32 tensor on the device of kv_cache");
+        ds = kv_descale->expand({bs});
+        p.kv_descale = ds.data_ptr<float>();
+        p.kv_descale_stride = ds.stride(0);
+    }
+    p.batch_size = bs;
+    p.seqlen_new = sn;
+    p.ckv_batch_stride = stride_or_zero(ckv, 0);
+    p.ckv_seqlen_stride = stride_or_zero(ckv, 1);
+    p.kpe_batch_stride = stride_or_zero(kpe, 0);
+    p.kpe_seqlen_stride = stride_or_zero(kpe, 1);
+    p.kv_page_stride = stride_or_zero(kv_cache, 0);
+    p.kv_row_stride = kv_cache.stride(1);
+    p.num_pages = kv_cache.size(0);
+    p.page_size = kv_cache.size(1);
+    p.max_pages = table.size(1);
+    p.block_table_stride = table.stride(0);
+    const int dtype = fa_dtype(ckv);
+    p.cache_dtype = fp8 ? FA_MLA_CACHE_E4M3 : dtype;
+    check_rc(fa_mla_append_gfx950(&p, dtype, current_stream(kv_cache)), "fa_mla_append_gfx950");
+    return new_seqlens;
 }
 
 }  // namespace flash_attention
@@ -1640,4 +1755,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_mla_decode_fwd", &flash_attention::flash_attention_mla_decode_fwd,
           "MLA decode over a paged latent KV cache (576 score / 512 value columns), returning (out, lse), gfx950");
     m.def("mla_version", []() { return fa_mla_version(); });
+    m.def("flash_attention_mla_decode_fp8_fwd", &flash_attention::flash_attention_mla_decode_fp8_fwd,
+          "MLA decode over a paged FP8 (e4m3) latent KV cache read in place, fp16 / bf16 q and o, (out, lse), gfx950");
+    m.def("flash_attention_mla_append", &flash_attention::flash_attention_mla_append,
+          "Append latent rows (c_kv || k_pe) to a paged latent KV cache, 16-bit or quantizing to e4m3, one HIP launch");
+    m.def("mla_fp8_version", []() { return fa_mla_fp8_version(); });
 }

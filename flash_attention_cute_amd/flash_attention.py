@@ -2109,7 +2109,7 @@ def flash_attention_mla_decode_forward_fake(q, kv_cache, block_table, cache_seql
 
 
 def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal=True, head_dim_v=512,
-                               return_lse=False, num_splits=0):
+                               return_lse=False, num_splits=0, kv_descale=None):
     """MLA decode over a paged latent KV cache, one HIP kernel (plus a small combine when the keys are split).
 
     ``q`` [B, Hq, Sq, 576] fp16 / bf16: the ABSORBED queries ``q_nope @ W_UK || q_pe`` (last stride 1).
@@ -2124,7 +2124,12 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
     Returns ``out`` [B, Hq, Sq, 512] (0 for a row without a visible key), and with ``return_lse`` also ``lse``
     fp32 [B, Hq, Sq] (natural log, -inf for such a row): the convention of ``flash_attn_paged_func(return_lse=True)``,
     so partial states go straight into ``flash_attn_merge_states``. ``num_splits``: 0 lets the plan choose the key
-    splits, n >= 1 forces n (capped at the plan's maximum)."""
+    splits, n >= 1 forces n (capped at the plan's maximum).
+
+    A ``torch.float8_e4m3fn`` ``kv_cache`` (576 bytes a row, row stride a multiple of 16) is read in place by the
+    FP8 kernel: ``q`` and ``out`` stay fp16 / bf16, and ``kv_descale`` (fp32 broadcastable to [B], a Python float,
+    or None = 1.0; read on the device) is one descale per batch row over all 576 columns: the result is that of
+    the 16-bit call over ``kv_cache.to(q.dtype) * kv_descale[b]`` without rounding that product."""
     if softmax_scale is None:
         raise TypeError("flash_attn_mla_decode_func needs softmax_scale: there is no default for MLA "
                         "(the absorbed head dim 576 is not the model's scale dim)")
@@ -2138,12 +2143,179 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
     if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
         raise ValueError(f"kv_cache must be [num_pages, page_size, 576], or 4-D with a singleton head axis "
                          f"(got {tuple(kv_cache.shape)})")
-    if kv_cache.dtype != q.dtype:
+    fp8 = _is_fp8_latent(kv_cache, kv_descale)
+    if fp8 and q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16 over a torch.float8_e4m3fn latent cache (got {q.dtype})")
+    if not fp8 and kv_cache.dtype != q.dtype:
         raise ValueError(f"q and kv_cache must have the same data type (got {q.dtype} and {kv_cache.dtype})")
     if kv_cache.size(1) % 32 != 0:
         raise ValueError(f"page_size must be a multiple of 32 (got {kv_cache.size(1)})")
     if num_splits < 0:
         raise ValueError(f"num_splits must be non-negative (got {num_splits})")
-    o, lse = torch.ops.flash_attention.mla_decode_forward(q, kv_cache, block_table, cache_seqlens,
-                                                          float(softmax_scale), bool(causal), int(num_splits))
+    if fp8:
+        o, lse = torch.ops.flash_attention.mla_decode_forward_fp8(
+            q, kv_cache, block_table, cache_seqlens, _latent_descale(kv_descale, q.size(0), q.device),
+            float(softmax_scale), bool(causal), int(num_splits))
+    else:
+        o, lse = torch.ops.flash_attention.mla_decode_forward(q, kv_cache, block_table, cache_seqlens,
+                                                              float(softmax_scale), bool(causal), int(num_splits))
     return (o, lse) if return_lse else o
+
+
+# ---------------------------------------------------------------------------------------------
+# The FP8 (OCP e4m3) latent cache and the latent cache's write side (include/fa_gfx950_mla_fp8.h): 576 bytes a
+# token with one descale per batch row over all 576 columns (vLLM's ``fp8`` MLA cache), read in place by
+# fa_mla_decode_fp8kv; ``flash_attn_mla_append`` is vLLM's ``concat_and_cache_mla`` under
+# ``flash_attn_kvcache_append``'s drop rules, copying into a 16-bit cache or quantizing into an e4m3 one.
+# ---------------------------------------------------------------------------------------------
+def _is_fp8_latent(kv_cache, kv_descale) -> bool:
+    """Whether the latent cache is the FP8 format the kernels serve; the wrappers' dtype errors."""
+    if kv_cache.dtype in _FP8_UNSUPPORTED:
+        raise ValueError(f"an 8-bit latent cache must be torch.float8_e4m3fn (OCP e4m3), not {kv_cache.dtype}")
+    fp8 = kv_cache.dtype == FP8_DTYPE
+    if not fp8 and kv_descale is not None:
+        raise ValueError(f"kv_descale goes with a torch.float8_e4m3fn latent cache, not {kv_cache.dtype}")
+    return fp8
+
+
+def _latent_descale(x, batch, device):
+    """None, or fp32 [B] (stride 0 for a scalar): ``_descale_arg`` with one kv head."""
+    if isinstance(x, torch.Tensor) and x.dim() == 1:  # [B] or [1]: the batch axis of _descale_arg's [B, Hkv]
+        x = x[:, None]
+    d = _descale_arg(x, "kv_descale", batch, 1, device)
+    return None if d is None else d[:, 0]
+
+
+@torch.library.custom_op("flash_attention::mla_decode_forward_fp8", mutates_args=())
+def flash_attention_mla_decode_forward_fp8(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                           cache_seqlens: torch.Tensor, kv_descale: Optional[torch.Tensor],
+                                           softmax_scale: float, causal: bool = True,
+                                           num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    # Non-GPU default: mla_decode_forward's default over the widened bytes, in fp32 so that folding the per-row
+    # descale into q and the output rounds nothing
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    d = (torch.ones(q.size(0), device=q.device) if kv_descale is None else kv_descale.float())[:, None, None, None]
+    o, lse = _mla_reference(q.float() * d, kv_cache.float(), block_table, cache_seqlens, softmax_scale, causal)
+    return (o * d).to(q.dtype), lse
+
+
+@torch.library.register_kernel("flash_attention::mla_decode_forward_fp8", "cuda")
+def flash_attention_mla_decode_forward_fp8_cuda(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                                cache_seqlens: torch.Tensor, kv_descale: Optional[torch.Tensor],
+                                                softmax_scale: float, causal: bool = True,
+                                                num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_mla_decode_fp8_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), kv_cache, block_table, cache_seqlens, kv_descale, softmax_scale,
+        causal, num_splits)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::mla_decode_forward_fp8")
+def flash_attention_mla_decode_forward_fp8_fake(q, kv_cache, block_table, cache_seqlens, kv_descale, softmax_scale,
+                                                causal=True, num_splits=0):
+    return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
+def _mla_append_reference(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale):
+    """The non-GPU default of the append ops: placement and drop rules of the kernel, vectorised."""
+    num_pages, page_size, _ = kv_cache.shape
+    cap = block_table.size(1) * page_size
+    b_, sn = c_kv.shape[:2]
+    lens = cache_seqlens.clamp(0, cap).to(torch.int64)
+    if b_ > 0 and sn > 0:
+        pos = lens[:, None] + torch.arange(sn, device=lens.device)[None]  # [B, Sn]
+        page = block_table.to(torch.int64).gather(1, pos.clamp(max=cap - 1) // page_size)
+        ok = (pos < cap) & (page >= 0) & (page < num_pages)
+        rows, dst = torch.cat([c_kv, k_pe], dim=-1), kv_cache
+        if kv_cache.dtype == FP8_DTYPE:  # (through byte views: index_put_ is not implemented for float8 tensors)
+            d = torch.ones(b_, device=rows.device) if kv_descale is None else kv_descale.float()
+            rows, dst = quantize_e4m3(rows, d[:, None, None]).view(torch.uint8), kv_cache.view(torch.uint8)
+        dst[page[ok], (pos % page_size)[ok]] = rows[ok]
+    return (lens + sn).clamp(max=cap).to(torch.int32)
+
+
+@torch.library.custom_op("flash_attention::mla_append", mutates_args=("kv_cache",))
+def flash_attention_mla_append(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                               cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    # kv_cache [num_pages, page_size, 576] of c_kv's dtype, c_kv [B, Sn, 512], k_pe [B, Sn, 64] -> new_seqlens [B]
+    return _mla_append_reference(kv_cache, c_kv, k_pe, cache_seqlens, block_table, None)
+
+
+@torch.library.register_kernel("flash_attention::mla_append", "cuda")
+def flash_attention_mla_append_cuda(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                                    cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    _require_ext()
+    return flash_attention_cuda.flash_attention_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, None)
+
+
+@torch.library.register_fake("flash_attention::mla_append")
+def flash_attention_mla_append_fake(kv_cache, c_kv, k_pe, cache_seqlens, block_table):
+    return torch.empty_like(cache_seqlens)
+
+
+@torch.library.custom_op("flash_attention::mla_append_fp8", mutates_args=("kv_cache",))
+def flash_attention_mla_append_fp8(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                                   cache_seqlens: torch.Tensor, block_table: torch.Tensor,
+                                   kv_descale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    # kv_cache [num_pages, page_size, 576] torch.float8_e4m3fn, kv_descale fp32 [B] or None -> new_seqlens [B]
+    return _mla_append_reference(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale)
+
+
+@torch.library.register_kernel("flash_attention::mla_append_fp8", "cuda")
+def flash_attention_mla_append_fp8_cuda(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                                        cache_seqlens: torch.Tensor, block_table: torch.Tensor,
+                                        kv_descale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _require_ext()
+    return flash_attention_cuda.flash_attention_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table,
+                                                           kv_descale)
+
+
+@torch.library.register_fake("flash_attention::mla_append_fp8")
+def flash_attention_mla_append_fp8_fake(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale=None):
+    return torch.empty_like(cache_seqlens)
+
+
+def flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale=None):
+    """Append latent rows to a paged latent KV cache in place, one HIP launch (vLLM's ``concat_and_cache_mla``).
+
+    ``c_kv`` [B, Sn, 512] and ``k_pe`` [B, Sn, 64] fp16 / bf16 (last stride 1); ``k_pe`` arrives ALREADY rotated
+    (DeepSeek's interleaved RoPE is not this project's rotate-half). Token i of sequence b goes to position
+    ``n = cache_seqlens[b] + i``: columns 0..511 and 512..575 of row ``n % page_size`` of page
+    ``block_table[b, n // page_size]`` of ``kv_cache`` [num_pages, page_size, 576]. The drop rules are
+    ``flash_attn_kvcache_append``'s: a write past ``max_pages * page_size`` or through a page id outside
+    ``[0, num_pages)`` is dropped, never redirected; negative lengths count as 0. A cache of the rows' dtype takes
+    their bits unchanged; a ``torch.float8_e4m3fn`` cache takes ``e4m3_rne(clamp(x / kv_descale[b], -448, 448))``
+    (``kv_descale``: fp32 broadcastable to [B], a Python float, or None = 1.0). The cache is never copied.
+
+    Returns ``new_seqlens = min(cache_seqlens + Sn, capacity)``, a NEW int32 [B]; ``cache_seqlens`` is not
+    modified. No host synchronisation (graph-capturable)."""
+    if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
+        raise ValueError(f"kv_cache must be [num_pages, page_size, 576] (got {tuple(kv_cache.shape)})")
+    if (c_kv.dim() != 3 or k_pe.dim() != 3 or c_kv.size(-1) != _MLA_DV or k_pe.size(-1) != _MLA_DQK - _MLA_DV
+            or c_kv.shape[:2] != k_pe.shape[:2]):
+        raise ValueError(f"c_kv must be [B, Sn, 512] and k_pe [B, Sn, 64] (got {tuple(c_kv.shape)} and "
+                         f"{tuple(k_pe.shape)})")
+    if c_kv.dtype != k_pe.dtype or c_kv.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"c_kv and k_pe must both be fp16 or both bf16 (got {c_kv.dtype} and {k_pe.dtype})")
+    if _is_fp8_latent(kv_cache, kv_descale):
+        return torch.ops.flash_attention.mla_append_fp8(kv_cache, c_kv, k_pe, cache_seqlens, block_table,
+                                                        _latent_descale(kv_descale, c_kv.size(0), kv_cache.device))
+    if kv_cache.dtype != c_kv.dtype:
+        raise ValueError(f"kv_cache must have the data type of c_kv or be torch.float8_e4m3fn (got {kv_cache.dtype} "
+                         f"and {c_kv.dtype})")
+    return torch.ops.flash_attention.mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table)
+
+
+def flash_attn_mla_with_kvcache(q, kv_cache, c_kv, k_pe, cache_seqlens, block_table, softmax_scale, causal=True,
+                                kv_descale=None, return_lse=False, return_seqlens=False, num_splits=0):
+    """One MLA serving step: ``flash_attn_mla_append`` of ``c_kv`` / ``k_pe``, then ``flash_attn_mla_decode_func``
+    of ``q`` [B, Hq, Sq, 576] over the advanced lengths -- two launches plus the combine, no host synchronisation.
+    Returns ``out``, followed by ``lse`` with ``return_lse`` and by ``new_seqlens`` with ``return_seqlens``;
+    ``cache_seqlens`` is not modified (the caller copies ``new_seqlens`` into it)."""
+    new_seqlens = flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale)
+    res = flash_attn_mla_decode_func(q, kv_cache, block_table, new_seqlens, softmax_scale, causal,
+                                     return_lse=return_lse, num_splits=num_splits, kv_descale=kv_descale)
+    if not return_seqlens:
+        return res
+    return (*res, new_seqlens) if return_lse else (res, new_seqlens)
