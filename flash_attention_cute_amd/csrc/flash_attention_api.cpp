@@ -35,6 +35,7 @@
 #include "fa_gfx950_lse.h"
 #include "fa_gfx950_mla.h"
 #include "fa_gfx950_mla_fp8.h"
+#include "fa_gfx950_mla_sparse.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
 #include "fa_gfx950_paged_varlen.h"
@@ -1509,11 +1510,17 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
 // kv_descale non-NULL (flash_attention_mla_decode_fp8_fwd, include/fa_gfx950_mla_fp8.h fa_mla_decode_fp8_gfx950): the
 // pool is torch.float8_e4m3fn bytes (row and page strides multiples of 16), q and o stay 16-bit, *kv_descale is fp32
 // broadcastable to [B] on q's device (read on the device through its stride, 0 for a scalar) or absent for 1.0.
+//
+// indices non-NULL (flash_attention_mla_sparse_decode_fwd, include/fa_gfx950_mla_sparse.h fa_mla_sparse_decode_gfx950):
+// int32 [B, Sq, topk] logical positions, topk a multiple of 32; row (b, hq, pos) attends over the visible entries of
+// list (b, pos) only. 16-bit pool only.
 std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch::Tensor &kv_cache,
                                                          torch::Tensor &block_table, torch::Tensor &cache_seqlens,
                                                          float softmax_scale, bool causal, int64_t num_splits,
-                                                         const c10::optional<torch::Tensor> *kv_descale) {
+                                                         const c10::optional<torch::Tensor> *kv_descale,
+                                                         const torch::Tensor *indices = nullptr) {
     const bool fp8 = kv_descale != nullptr;
+    TORCH_CHECK(!(fp8 && indices), "sparse MLA decode is built for a 16-bit latent cache only");
     TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 3,
                 "q must be 4-D [batch, heads, seqlen, 576], kv_cache 3-D [pages, page_size, 576]");
     TORCH_CHECK(q.size(3) == 576 && kv_cache.size(2) == 576, "MLA decode is built for 576 latent columns only");
@@ -1581,6 +1588,27 @@ std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch
     mp.causal = causal ? 1 : 0;
     const int dtype = fa_dtype(qx);
     void *stream = current_stream(qx);
+    if (indices) {
+        TORCH_CHECK(indices->dtype() == torch::kInt32 && indices->dim() == 3 && indices->size(0) == bs &&
+                        indices->size(1) == q.size(2),
+                    "indices must be int32 [batch, seqlen_q, topk]");
+        TORCH_CHECK(indices->size(2) > 0 && indices->size(2) % 32 == 0,
+                    "topk must be a positive multiple of 32 (pad the list with -1)");
+        TORCH_CHECK(indices->device() == q.device(), "indices must be on the device of q");
+        torch::Tensor ix = indices->stride(2) == 1 ? *indices : indices->contiguous();
+        fa_mla_sparse_params sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.base = mp;
+        sp.indices = ix.data_ptr<int32_t>();
+        sp.topk = ix.size(2);
+        sp.indices_batch_stride = stride_or_zero(ix, 0);
+        sp.indices_seqlen_stride = stride_or_zero(ix, 1);
+        launch_with_workspace(
+            "fa_mla_sparse_decode_gfx950", [&] { return fa_mla_sparse_decode_gfx950_ws_bytes(&sp); },
+            [&](void *ws, int64_t ws_bytes) { return fa_mla_sparse_decode_gfx950(&sp, dtype, ws, ws_bytes, stream); },
+            qx.options());
+        return {o, lse};
+    }
     if (fp8) {
         fa_mla_fp8_params fp;
         memset(&fp, 0, sizeof(fp));
@@ -1617,6 +1645,12 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_decode_fp8_fwd(
     torch::Tensor &q, torch::Tensor &kv_cache, torch::Tensor &block_table, torch::Tensor &cache_seqlens,
     c10::optional<torch::Tensor> kv_descale, float softmax_scale, bool causal, int64_t num_splits) {
     return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, &kv_descale);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_sparse_decode_fwd(
+    torch::Tensor &q, torch::Tensor &kv_cache, torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+    torch::Tensor &indices, float softmax_scale, bool causal, int64_t num_splits) {
+    return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, nullptr, &indices);
 }
 
 // The latent cache's write side (include/fa_gfx950_mla_fp8.h fa_mla_append_gfx950): c_kv [B, Sn, 512] and k_pe
@@ -1760,4 +1794,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_mla_append", &flash_attention::flash_attention_mla_append,
           "Append latent rows (c_kv || k_pe) to a paged latent KV cache, 16-bit or quantizing to e4m3, one HIP launch");
     m.def("mla_fp8_version", []() { return fa_mla_fp8_version(); });
+    m.def("flash_attention_mla_sparse_decode_fwd", &flash_attention::flash_attention_mla_sparse_decode_fwd,
+          "Sparse MLA decode over top-k token indices (int32 [B, Sq, topk]) of a paged latent KV cache, (out, lse), gfx950");
+    m.def("mla_sparse_version", []() { return fa_mla_sparse_version(); });
 }

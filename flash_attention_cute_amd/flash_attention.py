@@ -2108,8 +2108,61 @@ def flash_attention_mla_decode_forward_fake(q, kv_cache, block_table, cache_seql
     return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
 
 
+def _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale, causal):
+    """The non-GPU default of ``mla_sparse_decode_forward``, a float restatement: per (b, pos) the entries with
+    ``0 <= idx <= lim`` (``lim`` the dense call's: the clamped length - 1, with ``causal`` at most
+    ``pos + length - Sq``) are gathered through the table, duplicates as repeated rows; nothing else is read."""
+    b_, hq, sq, _ = q.shape
+    num_pages, page_size, _ = kv_cache.shape
+    cap = block_table.size(1) * page_size
+    out = torch.zeros((b_, hq, sq, _MLA_DV), dtype=torch.float32, device=q.device)
+    lse = torch.full((b_, hq, sq), float("-inf"), dtype=torch.float32, device=q.device)
+    for b, n in enumerate(cache_seqlens.tolist()):
+        n = min(max(n, 0), cap)
+        for pos in range(sq):
+            lim = min(n - 1, pos + n - sq) if causal else n - 1
+            idx = indices[b, pos].to(torch.int64)
+            idx = idx[(idx >= 0) & (idx <= lim)]
+            if idx.numel() == 0:
+                continue
+            pages = block_table[b].index_select(0, idx // page_size).clamp(0, num_pages - 1).to(torch.int64)
+            kv = kv_cache[pages, idx % page_size].float()
+            s = torch.matmul(q[b, :, pos].float(), kv.t()) * softmax_scale  # [Hq, n_visible]
+            l = torch.logsumexp(s, dim=-1)
+            out[b, :, pos], lse[b, :, pos] = torch.matmul(torch.exp(s - l[:, None]), kv[:, :_MLA_DV]), l
+    return out.to(q.dtype), lse
+
+
+@torch.library.custom_op("flash_attention::mla_sparse_decode_forward", mutates_args=())
+def flash_attention_mla_sparse_decode_forward(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                              cache_seqlens: torch.Tensor, indices: torch.Tensor,
+                                              softmax_scale: float, causal: bool = True,
+                                              num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    # q [B, Hq, Sq, 576], indices int32 [B, Sq, topk] -> (o [B, Hq, Sq, 512], lse fp32 [B, Hq, Sq])
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale, causal)
+
+
+@torch.library.register_kernel("flash_attention::mla_sparse_decode_forward", "cuda")
+def flash_attention_mla_sparse_decode_forward_cuda(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                                   cache_seqlens: torch.Tensor, indices: torch.Tensor,
+                                                   softmax_scale: float, causal: bool = True,
+                                                   num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_mla_sparse_decode_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), kv_cache if kv_cache.stride(-1) == 1 else kv_cache.contiguous(),
+        block_table, cache_seqlens, indices, softmax_scale, causal, num_splits)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::mla_sparse_decode_forward")
+def flash_attention_mla_sparse_decode_forward_fake(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale,
+                                                   causal=True, num_splits=0):
+    return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
 def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal=True, head_dim_v=512,
-                               return_lse=False, num_splits=0, kv_descale=None):
+                               return_lse=False, num_splits=0, kv_descale=None, indices=None):
     """MLA decode over a paged latent KV cache, one HIP kernel (plus a small combine when the keys are split).
 
     ``q`` [B, Hq, Sq, 576] fp16 / bf16: the ABSORBED queries ``q_nope @ W_UK || q_pe`` (last stride 1).
@@ -2129,7 +2182,20 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
     A ``torch.float8_e4m3fn`` ``kv_cache`` (576 bytes a row, row stride a multiple of 16) is read in place by the
     FP8 kernel: ``q`` and ``out`` stay fp16 / bf16, and ``kv_descale`` (fp32 broadcastable to [B], a Python float,
     or None = 1.0; read on the device) is one descale per batch row over all 576 columns: the result is that of
-    the 16-bit call over ``kv_cache.to(q.dtype) * kv_descale[b]`` without rounding that product."""
+    the 16-bit call over ``kv_cache.to(q.dtype) * kv_descale[b]`` without rounding that product.
+
+    ``indices`` (int32 [B, Sq, topk], last stride 1, ``topk`` a positive multiple of 32: pad with -1) makes the
+    call SPARSE, DeepSeek-V3.2's attention core (FlashMLA's ``indices=``), one HIP kernel of its own that gathers
+    the rows in place: row ``(b, hq, pos)`` attends over the entries of list ``(b, pos)`` only. An entry is a
+    LOGICAL position of sequence ``b`` (what the indexer produces), translated through ``block_table`` on the
+    device, and is a key iff ``0 <= idx <= lim``: ``lim = cache_seqlens[b] - 1`` without ``causal``,
+    ``min(cache_seqlens[b] - 1, pos + cache_seqlens[b] - Sq)`` with it (the dense call's bottom-right limit).
+    Every other value (-1, INT32_MAX, past the length, past the causal limit) is not a key: no pool row is read
+    for it and it contributes exactly nothing. The list is unsorted; a duplicate counts once per occurrence. A
+    row without a visible entry gives ``out`` 0 and ``lse`` -inf; the lse merges with
+    ``flash_attn_merge_states``, so a list sharded over devices is expressible. ``num_splits`` then splits a
+    list's ``topk / 32`` tiles. 16-bit cache only: with an FP8 cache or ``kv_descale`` it raises
+    ``NotImplementedError``. ``indices=None`` is the dense call."""
     if softmax_scale is None:
         raise TypeError("flash_attn_mla_decode_func needs softmax_scale: there is no default for MLA "
                         "(the absorbed head dim 576 is not the model's scale dim)")
@@ -2143,6 +2209,9 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
     if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
         raise ValueError(f"kv_cache must be [num_pages, page_size, 576], or 4-D with a singleton head axis "
                          f"(got {tuple(kv_cache.shape)})")
+    if indices is not None and (kv_descale is not None or kv_cache.dtype == FP8_DTYPE):
+        raise NotImplementedError("sparse MLA decode (indices=) is built for a 16-bit latent cache only: "
+                                  "no FP8 cache and no kv_descale")
     fp8 = _is_fp8_latent(kv_cache, kv_descale)
     if fp8 and q.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"q must be fp16 or bf16 over a torch.float8_e4m3fn latent cache (got {q.dtype})")
@@ -2152,7 +2221,14 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
         raise ValueError(f"page_size must be a multiple of 32 (got {kv_cache.size(1)})")
     if num_splits < 0:
         raise ValueError(f"num_splits must be non-negative (got {num_splits})")
-    if fp8:
+    if indices is not None:
+        if (indices.dtype != torch.int32 or indices.dim() != 3 or tuple(indices.shape[:2]) != (q.size(0), q.size(2))
+                or indices.size(2) == 0 or indices.size(2) % 32 != 0):
+            raise ValueError(f"indices must be int32 [B, Sq, topk] = [{q.size(0)}, {q.size(2)}, a positive multiple "
+                             f"of 32] (pad the list with -1; got {indices.dtype} {tuple(indices.shape)})")
+        o, lse = torch.ops.flash_attention.mla_sparse_decode_forward(
+            q, kv_cache, block_table, cache_seqlens, indices, float(softmax_scale), bool(causal), int(num_splits))
+    elif fp8:
         o, lse = torch.ops.flash_attention.mla_decode_forward_fp8(
             q, kv_cache, block_table, cache_seqlens, _latent_descale(kv_descale, q.size(0), q.device),
             float(softmax_scale), bool(causal), int(num_splits))
@@ -2308,14 +2384,19 @@ def flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_d
 
 
 def flash_attn_mla_with_kvcache(q, kv_cache, c_kv, k_pe, cache_seqlens, block_table, softmax_scale, causal=True,
-                                kv_descale=None, return_lse=False, return_seqlens=False, num_splits=0):
+                                kv_descale=None, return_lse=False, return_seqlens=False, num_splits=0, indices=None):
     """One MLA serving step: ``flash_attn_mla_append`` of ``c_kv`` / ``k_pe``, then ``flash_attn_mla_decode_func``
     of ``q`` [B, Hq, Sq, 576] over the advanced lengths -- two launches plus the combine, no host synchronisation.
     Returns ``out``, followed by ``lse`` with ``return_lse`` and by ``new_seqlens`` with ``return_seqlens``;
-    ``cache_seqlens`` is not modified (the caller copies ``new_seqlens`` into it)."""
+    ``cache_seqlens`` is not modified (the caller copies ``new_seqlens`` into it). ``indices`` (int32
+    [B, Sq, topk], see ``flash_attn_mla_decode_func``) makes the decode sparse; its entries refer to the cache
+    AFTER the append (positions of the new tokens included)."""
+    if indices is not None and (kv_descale is not None or kv_cache.dtype == FP8_DTYPE):  # (before the cache is written)
+        raise NotImplementedError("sparse MLA decode (indices=) is built for a 16-bit latent cache only")
     new_seqlens = flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale)
     res = flash_attn_mla_decode_func(q, kv_cache, block_table, new_seqlens, softmax_scale, causal,
-                                     return_lse=return_lse, num_splits=num_splits, kv_descale=kv_descale)
+                                     return_lse=return_lse, num_splits=num_splits, kv_descale=kv_descale,
+                                     indices=indices)
     if not return_seqlens:
         return res
     return (*res, new_seqlens) if return_lse else (res, new_seqlens)
