@@ -16,7 +16,7 @@ into the package directory so the artefacts travel with the repository snapshot.
      csrc/fa_mla_gfx950.hip, csrc/fa_mla_fp8_gfx950.hip, csrc/fa_mla_append.hip, csrc/fa_mla_sparse_gfx950.hip
      (stand-alone kernels with their entries; the last four are the MLA decode over a paged latent cache, the same
      over an FP8 (e4m3) latent cache, the latent cache's append, and the sparse MLA decode over top-k token
-     indices, both dtypes in each file)
+     indices, both dtypes in each file; the three decodes share the host layer of csrc/fa_mla_host.h)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
      include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h,
      include/fa_gfx950_paged_prefill.h, include/fa_gfx950_lse.h, include/fa_gfx950_paged_varlen.h,
@@ -170,7 +170,8 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     objs = []
     asm_files = []
     tooling = [Path(__file__).resolve()]
-    headers = [*sorted(CSRC.glob("*.h")), *sorted(INCLUDE.glob("*.h"))]
+    # every file a source can include: the device code of the kernels lives in csrc/*.hpp, that of the stand-alone
+    # MLA sources too (fa_mla_*.hpp, fa_decode.hpp, fa_fwd_kernels.hpp), so one list serves both kinds of unit
     inst_deps = ([p for ext in ("*.hpp", "*.h", "*.inc") for p in sorted(CSRC.glob(ext))]
                  + sorted(INCLUDE.glob("*.h")))
     for prefix, name in INST_TUS:
@@ -190,8 +191,9 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
                          inst_deps + [CSRC / f"{name}.hip"] + tooling))
     # C-ABI dispatchers (dense, paged decode, paged prefill, paged decode with LSE, ragged paged prefill, paged decode
     # with sinks, ragged paged prefill with sinks, ragged paged prefill with the LSE), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel,
-    # MLA decode (kernel, plan, combine and entries in one file), the same over an FP8 latent cache, the latent append,
-    # the sparse MLA decode over top-k token indices
+    # MLA decode (checks, kernel selection and entries; the kernels are fa_mla_decode.hpp's, the plan, workspace and
+    # launch fa_mla_host.h's), the same over an FP8 latent cache, the latent append, the sparse MLA decode over top-k
+    # token indices
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_paged_lse_gfx950.hip",
                 "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip",
                 "fa_paged_varlen_lse_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
@@ -201,7 +203,7 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *SOURCE_FLAGS.get(src, []), *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src,
                       "-o", obj], obj,
-                     [CSRC / src, *headers, *tooling]))
+                     [CSRC / src, *inst_deps, *tooling]))
 
     def compile_one(cmd, obj, deps):
         stamp = obj.with_suffix(".cmd")

@@ -49,7 +49,7 @@ constexpr int kMlaTile = kDecKeys * kMlaRowBytes;      // 36 KiB
 constexpr int kMlaPieces = kMlaTile / 1024 / 4;        // LDS-DMA pieces per wave per tile: 9
 constexpr int kMlaKSteps = kMlaDqk / 16 / 4;           // k-steps of a wave's score columns: 9
 constexpr int kMlaDTiles = kMlaDv / 32 / 4;            // d-tiles of a wave's output columns: 4
-// The plan (fa_mla_gfx950.hip): about one workgroup per CU of an MI355X (the ring admits one per CU, and a
+// The plan (mla_plan, fa_mla_host.h): about one workgroup per CU of an MI355X (the ring admits one per CU, and a
 // workgroup's tile rate is bound by its own barrier-separated phases, not by HBM: 256 measured faster than the
 // decode kernels' 160 on every shape, and 64 slower), a split at least 8 tiles of the table's capacity, at most
 // 256 splits (one long sequence still fills the device; fa_mla_combine has one thread per split)

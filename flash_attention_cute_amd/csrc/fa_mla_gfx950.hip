@@ -1,11 +1,12 @@
 // fa_mla_gfx950.hip -- C-ABI of the MLA decode over a paged latent KV cache (include/fa_gfx950_mla.h): the
-// checks, the split plan, the launches of fa_mla_decode / fa_mla_combine (fa_mla_decode.hpp) for both dtypes,
-// and the entries. A translation unit of its own beside the dispatchers (whose error channel it uses
-// through fa_launch.h); no other file references its kernels.
+// checks, the selection of fa_mla_decode (fa_mla_decode.hpp) for both dtypes, and the entries. The plan, the
+// workspace, the argument fill and the launch with fa_mla_combine are fa_mla_host.h's, shared with the FP8 and
+// sparse entries. A translation unit of its own beside the dispatchers (whose error channel it uses through
+// fa_launch.h); no other file references its kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fa_mla_decode.hpp"
+#include "fa_mla_host.h"
 
 namespace fa {
 namespace {
@@ -57,38 +58,14 @@ int mla_check(const fa_mla_params *p, int dtype) {
     return FA_OK;
 }
 
-// The plan: every split takes an equal share of each sequence's tiles (the kernel's k_lo rule); the split
-// count makes the workgroups about kMlaTargetWgs, each split at least kMlaMinTilesPerSplit tiles of the
-// table's capacity, at most kMlaMaxSplit -- or what num_splits forces.
-MlaArgs mla_plan(const fa_mla_params &p) {
-    MlaArgs a{};
-    a.rows = (int)(p.num_heads_q * p.seqlen_q);
-    a.n_rg = (a.rows + kMlaGroupRows - 1) / kMlaGroupRows;
-    const int64_t n_tiles = p.max_pages * p.page_size / kDecKeys;
-    const int64_t wgs = (p.batch_size > 0 ? p.batch_size : 1) * a.n_rg;
-    int64_t ns = (kMlaTargetWgs + wgs - 1) / wgs;
-    const int64_t by_len = n_tiles / kMlaMinTilesPerSplit;
-    ns = ns < by_len ? ns : by_len;
-    if (p.num_splits > 0) ns = p.num_splits;
-    ns = ns < kMlaMaxSplit ? ns : kMlaMaxSplit;
-    a.n_split = (int)(ns < 1 ? 1 : ns);
-    return a;
-}
-
-int64_t mla_ws_bytes(const fa_mla_params &p, const MlaArgs &a) {
-    return a.n_split > 1 ? p.batch_size * a.n_split * a.rows * (int64_t)(kMlaDv * 4 + 4) : 0;
-}
-
 template <class DT>
-void mla_launch_kernels(const MlaArgs &a, hipStream_t stream) {
-    const int64_t units = (int64_t)a.batch * a.n_split;
-    const dim3 grid((uint32_t)(8 * ((units + 7) / 8) * a.n_rg));
-    if (a.rows <= kDecRows)  // one row block: the kernel without the second block's registers
-        hipLaunchKernelGGL((fa_mla_decode<DT, 1>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((fa_mla_decode<DT, 2>), grid, dim3(256), 0, stream, a);
-    if (a.n_split > 1)
-        hipLaunchKernelGGL((fa_mla_combine<DT>), dim3((uint32_t)(4 * a.batch * a.rows)), dim3(256), 0, stream, a);
+int mla_launch_kernels(const MlaArgs &a, hipStream_t stream) {
+    return mla_run<DT>(a, (int64_t)a.batch * a.n_split, stream, [&](const dim3 grid) {
+        if (a.rows <= kDecRows)  // one row block: the kernel without the second block's registers
+            hipLaunchKernelGGL((fa_mla_decode<DT, 1>), grid, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL((fa_mla_decode<DT, 2>), grid, dim3(256), 0, stream, a);
+    });
 }
 
 int mla_launch(const fa_mla_params *params, int dtype, void *ws, int64_t ws_bytes, hipStream_t stream) {
@@ -96,32 +73,11 @@ int mla_launch(const fa_mla_params *params, int dtype, void *ws, int64_t ws_byte
     if (rc != FA_OK) return rc;
     const fa_mla_params &p = *params;
     MlaArgs a = mla_plan(p);
-    const int64_t need = mla_ws_bytes(p, a);
-    if (need > 0 && (!ws || ws_bytes < need))
-        return set_err(FA_ERR_INVALID_ARGUMENT, "workspace of %lld bytes is smaller than the %lld required",
-                       (long long)(ws ? ws_bytes : 0), (long long)need);
-    if ((uintptr_t)ws & 15) return set_err(FA_ERR_INVALID_ARGUMENT, "workspace must be 16-byte aligned");
+    const int wrc = mla_bind_ws(a, p.batch_size, ws, ws_bytes);
+    if (wrc != FA_OK) return wrc;
     if (p.batch_size == 0) return FA_OK;
-    a.q = (const char *)p.q_ptr, a.kv = (const char *)p.kv_ptr, a.o = (char *)p.o_ptr, a.lse = p.lse_ptr;
-    a.block_table = p.block_table, a.seqlens_k = p.seqlens_k;
-    a.q_bs = p.q_batch_stride, a.q_hs = p.q_head_stride, a.q_ss = p.q_seqlen_stride;
-    a.o_bs = p.o_batch_stride, a.o_hs = p.o_head_stride, a.o_ss = p.o_seqlen_stride;
-    a.lse_bs = p.lse_batch_stride, a.lse_hs = p.lse_head_stride, a.lse_ss = p.lse_seqlen_stride;
-    a.kv_ps = p.kv_page_stride, a.kv_rs = (int)p.kv_row_stride;
-    a.batch = (int)p.batch_size, a.Sq = (int)p.seqlen_q;
-    a.num_pages = (int)p.num_pages, a.tiles_per_page = (int)(p.page_size / kDecKeys);
-    a.cap_keys = (int)(p.max_pages * p.page_size), a.bt_stride = (int)p.block_table_stride;
-    a.causal = p.causal != 0 && p.seqlen_q > 1;
-    a.sc = p.softmax_scale;
-    if (need > 0) {
-        a.ws_o = (float *)ws;
-        a.ws_lse = (float *)((char *)ws + p.batch_size * a.n_split * a.rows * (int64_t)(kMlaDv * 4));
-    }
-    if (dtype == FA_DTYPE_F16) mla_launch_kernels<F16>(a, stream);
-    else mla_launch_kernels<BF16>(a, stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-    return FA_OK;
+    mla_fill_args(a, p);  // (kv_rs in 16-bit elements)
+    return dtype == FA_DTYPE_F16 ? mla_launch_kernels<F16>(a, stream) : mla_launch_kernels<BF16>(a, stream);
 }
 
 }  // namespace
@@ -136,6 +92,7 @@ extern "C" int fa_mla_decode_gfx950_check(const fa_mla_params *params, int dtype
 }
 extern "C" int64_t fa_mla_decode_gfx950_ws_bytes(const fa_mla_params *params) {
     if (fa::mla_check(params, FA_DTYPE_F16) != FA_OK) return -1;
-    return fa::mla_ws_bytes(*params, fa::mla_plan(*params));
+    const fa::MlaArgs a = fa::mla_plan(*params);
+    return fa::mla_ws_bytes(params->batch_size, a.n_split, a.rows);
 }
 extern "C" int fa_mla_version(void) { return FA_GFX950_MLA_VERSION; }

@@ -249,3 +249,22 @@ def test_mla_plan_splits_one_long_sequence_and_honours_num_splits(lib):
     assert lib.fa_mla_decode_gfx950_ws_bytes(ctypes.byref(mla_params(num_splits=1))) == 0
     assert lib.fa_mla_decode_gfx950_ws_bytes(ctypes.byref(mla_params(b=2, hq=24, sq=3, num_splits=3))) == \
         2 * 3 * 72 * (512 * 4 + 4)
+
+
+# (shape -> workspace bytes) as the library answered before the three entries shared one plan: the split rule (256
+# workgroups over B * row groups, a split at least 8 tiles of the table's capacity, at most 256) times 2052 bytes per
+# (batch, split, row). Rows: the 8-tile minimum on either side (15 / 16 tiles) and deciding (130 tiles); the
+# row-group boundary Hq * Sq = 64 / 65, by heads and by positions; the workgroup target deciding at B 32; a batch
+# that needs no split; a forced split count above the 256 cap, and one below; a page of 96; an empty batch.
+WS_BYTES = [({}, 525312), (dict(max_pages=4), 0), (dict(max_pages=15), 0), (dict(max_pages=16), 65664),
+            (dict(hq=64), 2101248), (dict(hq=65), 2134080), (dict(hq=16, sq=4), 2101248), (dict(hq=13, sq=5), 2134080),
+            (dict(b=32, hq=128, max_pages=64), 33619968), (dict(b=32, hq=16, page=64, max_pages=63), 8404992),
+            (dict(b=4096, hq=1, max_pages=4096), 0), (dict(num_splits=300), 8404992),
+            (dict(b=2, hq=24, sq=3, num_splits=3), 886464), (dict(page=96, max_pages=7), 65664),
+            (dict(b=0, num_pages=1, num_splits=3), 0)]
+
+
+@pytest.mark.parametrize("kw,ws_bytes", WS_BYTES, ids=[",".join(f"{k}={v}" for k, v in kw.items()) or "default"
+                                                       for kw, _ in WS_BYTES])
+def test_mla_ws_bytes_table(lib, kw, ws_bytes):
+    assert lib.fa_mla_decode_gfx950_ws_bytes(ctypes.byref(mla_params(**kw))) == ws_bytes

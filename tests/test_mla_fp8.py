@@ -16,7 +16,8 @@ import pytest
 import torch
 
 from test_abi import FA_ERR_INVALID_ARGUMENT, FA_ERR_UNSUPPORTED, FA_OK
-from test_mla_decode import BF16, F16, LENS32, LENS64, SCALE, FaMlaParams, check, lib, mla_params  # noqa: F401
+from test_mla_decode import (BF16, F16, LENS32, LENS64, SCALE, WS_BYTES, FaMlaParams, check, lib,  # noqa: F401
+                             mla_params)
 
 FP8, NAN_BYTE, SENTINEL = torch.float8_e4m3fn, 0x7F, 0x5A
 
@@ -307,3 +308,12 @@ def test_mla_fp8_check_codes(lib, kw, descale_stride, code):  # noqa: F811
             lib.fa_mla_decode_gfx950_ws_bytes(ctypes.byref(p.base)) > 0
     assert lib.fa_mla_decode_fp8_gfx950_check(None, 1) == FA_ERR_INVALID_ARGUMENT
     assert lib.fa_mla_fp8_version() == 1
+
+
+def test_mla_fp8_ws_bytes_is_the_dense_entrys(lib):  # noqa: F811
+    """One plan: on every row of the dense entry's table the FP8 entry asks for the same workspace."""
+    lib.fa_mla_decode_fp8_gfx950_ws_bytes.restype = ctypes.c_int64
+    for kw, ws_bytes in WS_BYTES:
+        p = FaMlaFp8Params(mla_params(**kw), 0x700000, 1)
+        assert lib.fa_mla_decode_fp8_gfx950_ws_bytes(ctypes.byref(p)) == ws_bytes == \
+            lib.fa_mla_decode_gfx950_ws_bytes(ctypes.byref(p.base)), kw

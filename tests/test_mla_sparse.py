@@ -213,3 +213,26 @@ def test_mla_sparse_check_codes_and_workspace(kw, code):
     assert lib.fa_mla_sparse_decode_gfx950_ws_bytes(ctypes.byref(sparse_params(num_splits=1))) == 0
     assert lib.fa_mla_sparse_decode_gfx950_ws_bytes(ctypes.byref(sparse_params(b=2, hq=24, sq=3, num_splits=3))) == \
         2 * 3 * 24 * 3 * (512 * 4 + 4)
+
+
+# (shape, topk -> workspace bytes) as the library answered before the three entries shared one plan: the dense
+# rule over B * Sq * head groups and the list's topk / 32 tiles, a split at least 2 tiles. Rows: the 2-tile minimum
+# deciding (topk 256: 4 splits of 2 tiles, where the dense entry's 8-tile minimum would not split; topk 160: 5 tiles,
+# 2 splits) and forbidding a split (topk 64, 32); the workgroup target deciding (B 32, B 64); the head-group boundary
+# Hq = 64 / 65; positions, which multiply the workgroups and not the head groups; a forced split count above the
+# 256 cap, and one below.
+SPARSE_WS_BYTES = [({}, 2048, 1050624), ({}, 256, 131328), ({}, 160, 65664), ({}, 64, 0), ({}, 32, 0),
+                   (dict(b=64), 256, 8404992), (dict(hq=64), 2048, 4202496), (dict(hq=65), 2048, 4268160),
+                   (dict(hq=16, sq=4), 2048, 4202496), (dict(hq=128, sq=2), 256, 2101248),
+                   (dict(b=32, hq=128), 2048, 33619968), (dict(b=32, hq=16, sq=2), 2048, 8404992),
+                   (dict(num_splits=300), 2048, 8404992), (dict(b=2, hq=24, sq=3, num_splits=3), 2048, 886464)]
+
+
+@pytest.mark.parametrize("kw,topk,ws_bytes", SPARSE_WS_BYTES, ids=[
+    ",".join(f"{k}={v}" for k, v in {**kw, "topk": topk}.items()) for kw, topk, _ in SPARSE_WS_BYTES])
+def test_mla_sparse_ws_bytes_table(kw, topk, ws_bytes):
+    if not LIB.exists():
+        pytest.skip("libfa_gfx950.so not built (run __graft_entry__.build())")
+    lib = ctypes.CDLL(str(LIB))
+    lib.fa_mla_sparse_decode_gfx950_ws_bytes.restype = ctypes.c_int64
+    assert lib.fa_mla_sparse_decode_gfx950_ws_bytes(ctypes.byref(sparse_params(topk=topk, **kw))) == ws_bytes
