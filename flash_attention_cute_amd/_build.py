@@ -13,16 +13,18 @@ into the package directory so the artefacts travel with the repository snapshot.
      csrc/fa_paged_varlen_gfx950.hip, csrc/fa_paged_sink_gfx950.hip, csrc/fa_paged_varlen_sink_gfx950.hip,
      csrc/fa_paged_varlen_lse_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip,
      csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip, csrc/fa_kvcache_varlen.hip, csrc/fa_merge.hip,
-     csrc/fa_mla_gfx950.hip, csrc/fa_mla_fp8_gfx950.hip, csrc/fa_mla_append.hip, csrc/fa_mla_sparse_gfx950.hip
-     (stand-alone kernels with their entries; the last four are the MLA decode over a paged latent cache, the same
-     over an FP8 (e4m3) latent cache, the latent cache's append, and the sparse MLA decode over top-k token
-     indices, both dtypes in each file; the three decodes share the host layer of csrc/fa_mla_host.h)
+     csrc/fa_mla_gfx950.hip, csrc/fa_mla_fp8_gfx950.hip, csrc/fa_mla_append.hip, csrc/fa_mla_sparse_gfx950.hip,
+     csrc/fa_mla_sparse_mixed_gfx950.hip, csrc/fa_mla_append_mixed.hip
+     (stand-alone kernels with their entries; the last six are the MLA decode over a paged latent cache, the same
+     over an FP8 (e4m3) latent cache, the latent cache's append, the sparse MLA decode over top-k token
+     indices, both dtypes in each file, and the sparse decode and the append on DeepSeek-V3.2's mixed FP8 row, bf16;
+     the four decodes share the host layer of csrc/fa_mla_host.h)
      ->  lib/libfa_gfx950.so (the C-ABI library of include/fa_gfx950.h, include/fa_gfx950_paged.h,
      include/fa_gfx950_kvcache.h, include/fa_gfx950_fp8.h, include/fa_gfx950_paged_window.h,
      include/fa_gfx950_paged_prefill.h, include/fa_gfx950_lse.h, include/fa_gfx950_paged_varlen.h,
      include/fa_gfx950_kvcache_varlen.h, include/fa_gfx950_sink.h, include/fa_gfx950_paged_varlen_sink.h,
-     include/fa_gfx950_paged_varlen_lse.h, include/fa_gfx950_mla.h, include/fa_gfx950_mla_fp8.h and
-     include/fa_gfx950_mla_sparse.h; no torch symbols)
+     include/fa_gfx950_paged_varlen_lse.h, include/fa_gfx950_mla.h, include/fa_gfx950_mla_fp8.h,
+     include/fa_gfx950_mla_sparse.h and include/fa_gfx950_mla_mixed.h; no torch symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -109,7 +111,8 @@ HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mcode-obj
 # (v_pk_{add,mul,fma}_f32), whose every use would otherwise have to be vetted form by form
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"fa_mla_gfx950.hip": _NO_PK_F32, "fa_mla_fp8_gfx950.hip": _NO_PK_F32, "fa_mla_append.hip": _NO_PK_F32,
-                "fa_mla_sparse_gfx950.hip": _NO_PK_F32}
+                "fa_mla_sparse_gfx950.hip": _NO_PK_F32, "fa_mla_sparse_mixed_gfx950.hip": _NO_PK_F32,
+                "fa_mla_append_mixed.hip": _NO_PK_F32}
 
 
 def _jobs() -> int:
@@ -193,12 +196,13 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     # with sinks, ragged paged prefill with sinks, ragged paged prefill with the LSE), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel,
     # MLA decode (checks, kernel selection and entries; the kernels are fa_mla_decode.hpp's, the plan, workspace and
     # launch fa_mla_host.h's), the same over an FP8 latent cache, the latent append, the sparse MLA decode over top-k
-    # token indices
+    # token indices, the sparse decode and the append on the mixed FP8 row
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_paged_lse_gfx950.hip",
                 "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip",
                 "fa_paged_varlen_lse_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
                 "fa_kvcache_varlen.hip", "fa_merge.hip", "fa_mla_gfx950.hip", "fa_mla_fp8_gfx950.hip",
-                "fa_mla_append.hip", "fa_mla_sparse_gfx950.hip"):
+                "fa_mla_append.hip", "fa_mla_sparse_gfx950.hip", "fa_mla_sparse_mixed_gfx950.hip",
+                "fa_mla_append_mixed.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *SOURCE_FLAGS.get(src, []), *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src,

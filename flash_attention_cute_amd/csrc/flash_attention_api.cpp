@@ -35,6 +35,7 @@
 #include "fa_gfx950_lse.h"
 #include "fa_gfx950_mla.h"
 #include "fa_gfx950_mla_fp8.h"
+#include "fa_gfx950_mla_mixed.h"
 #include "fa_gfx950_mla_sparse.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
@@ -1513,22 +1514,30 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_kvcache_append_varlen(
 //
 // indices non-NULL (flash_attention_mla_sparse_decode_fwd, include/fa_gfx950_mla_sparse.h fa_mla_sparse_decode_gfx950):
 // int32 [B, Sq, topk] logical positions, topk a multiple of 32; row (b, hq, pos) attends over the visible entries of
-// list (b, pos) only. 16-bit pool only.
+// list (b, pos) only. 16-bit pool, or (flash_attention_mla_sparse_mixed_decode_fwd, include/fa_gfx950_mla_mixed.h
+// fa_mla_sparse_mixed_decode_gfx950) a torch.uint8 pool [num_pages, page_size, 656] of mixed rows (512 e4m3 bytes, four
+// fp32 tile scales, 64 bf16 RoPE columns; row and page strides multiples of 16) with bf16 q; never copied.
 std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch::Tensor &kv_cache,
                                                          torch::Tensor &block_table, torch::Tensor &cache_seqlens,
                                                          float softmax_scale, bool causal, int64_t num_splits,
                                                          const c10::optional<torch::Tensor> *kv_descale,
-                                                         const torch::Tensor *indices = nullptr) {
+                                                         const torch::Tensor *indices = nullptr,
+                                                         const bool mixed = false) {
     const bool fp8 = kv_descale != nullptr;
-    TORCH_CHECK(!(fp8 && indices), "sparse MLA decode is built for a 16-bit latent cache only");
+    const int64_t row_width = mixed ? FA_MLA_MIXED_ROW_BYTES : 576;
+    TORCH_CHECK(!(fp8 && indices), "sparse MLA decode is built for a 16-bit or a mixed-row latent cache only");
+    TORCH_CHECK(!mixed || (indices && kv_cache.dtype() == torch::kUInt8),
+                "a mixed-row latent cache is torch.uint8 and is read by the sparse decode (indices) only");
     TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 3,
                 "q must be 4-D [batch, heads, seqlen, 576], kv_cache 3-D [pages, page_size, 576]");
-    TORCH_CHECK(q.size(3) == 576 && kv_cache.size(2) == 576, "MLA decode is built for 576 latent columns only");
+    TORCH_CHECK(q.size(3) == 576 && kv_cache.size(2) == row_width,
+                "MLA decode is built for 576 latent columns (656 bytes of a mixed row) only");
+    TORCH_CHECK(!mixed || q.dtype() == torch::kBFloat16, "q must be bf16 over a mixed-row latent cache");
     TORCH_CHECK(q.size(0) > 0 && q.size(1) > 0 && q.size(2) > 0, "q must have at least one element");
     TORCH_CHECK(kv_cache.size(0) > 0 && kv_cache.size(1) > 0 && kv_cache.size(1) % 32 == 0,
                 "page_size must be a positive multiple of 32");
     TORCH_CHECK(!fp8 || kv_cache.dtype() == torch::kFloat8_e4m3fn, "an fp8 latent cache must be torch.float8_e4m3fn");
-    TORCH_CHECK(fp8 || q.dtype() == kv_cache.dtype(), "q and kv_cache must have the same data type");
+    TORCH_CHECK(fp8 || mixed || q.dtype() == kv_cache.dtype(), "q and kv_cache must have the same data type");
     TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16, "q, kv_cache only support fp16 or bf16 data type");
     TORCH_CHECK(q.stride(3) == 1 && kv_cache.stride(2) == 1, "q, kv_cache must be contiguous in the last dimension");
     TORCH_CHECK(num_splits >= 0, "num_splits must be non-negative");
@@ -1544,12 +1553,12 @@ std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch
     require_gfx950(q.device());
 
     torch::Tensor qx = aligned_or_contiguous(q);
-    const int64_t kv_unit = fp8 ? 16 : 8;
+    const int64_t kv_unit = fp8 || mixed ? 16 : 8;
     const bool kv_ok = reinterpret_cast<uintptr_t>(kv_cache.data_ptr()) % 16 == 0 && kv_cache.stride(1) % kv_unit == 0 &&
                        (kv_cache.stride(0) % kv_unit == 0 || kv_cache.size(0) == 1) && kv_cache.stride(0) >= 0 &&
-                       kv_cache.stride(1) >= 576;
-    // (an fp8 pool is never copied: a layout the library does not take is its error)
-    torch::Tensor kvx = kv_ok || fp8 ? kv_cache : kv_cache.contiguous();
+                       kv_cache.stride(1) >= row_width;
+    // (an fp8 or mixed pool is never copied: a layout the library does not take is its error)
+    torch::Tensor kvx = kv_ok || fp8 || mixed ? kv_cache : kv_cache.contiguous();
     torch::Tensor table = table_with_contiguous_rows(block_table), lens = cache_seqlens.contiguous();
     torch::Tensor o = torch::empty({bs, q.size(1), q.size(2), 512}, q.options());
     torch::Tensor lse = torch::empty({bs, q.size(1), q.size(2)}, q.options().dtype(torch::kFloat32));
@@ -1603,6 +1612,15 @@ std::tuple<torch::Tensor, torch::Tensor> mla_decode_impl(torch::Tensor &q, torch
         sp.topk = ix.size(2);
         sp.indices_batch_stride = stride_or_zero(ix, 0);
         sp.indices_seqlen_stride = stride_or_zero(ix, 1);
+        if (mixed) {
+            launch_with_workspace(
+                "fa_mla_sparse_mixed_decode_gfx950", [&] { return fa_mla_sparse_mixed_decode_gfx950_ws_bytes(&sp); },
+                [&](void *ws, int64_t ws_bytes) {
+                    return fa_mla_sparse_mixed_decode_gfx950(&sp, dtype, ws, ws_bytes, stream);
+                },
+                qx.options());
+            return {o, lse};
+        }
         launch_with_workspace(
             "fa_mla_sparse_decode_gfx950", [&] { return fa_mla_sparse_decode_gfx950_ws_bytes(&sp); },
             [&](void *ws, int64_t ws_bytes) { return fa_mla_sparse_decode_gfx950(&sp, dtype, ws, ws_bytes, stream); },
@@ -1653,22 +1671,35 @@ std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_sparse_decode_fwd(
     return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, nullptr, &indices);
 }
 
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_sparse_mixed_decode_fwd(
+    torch::Tensor &q, torch::Tensor &kv_cache, torch::Tensor &block_table, torch::Tensor &cache_seqlens,
+    torch::Tensor &indices, float softmax_scale, bool causal, int64_t num_splits) {
+    return mla_decode_impl(q, kv_cache, block_table, cache_seqlens, softmax_scale, causal, num_splits, nullptr, &indices,
+                           true);
+}
+
 // The latent cache's write side (include/fa_gfx950_mla_fp8.h fa_mla_append_gfx950): c_kv [B, Sn, 512] and k_pe
 // [B, Sn, 64] (already rotated) of one 16-bit dtype go to rows cache_seqlens[b] .. of sequence b in kv_cache
 // [num_pages, page_size, 576], which has their dtype (the bits are copied) or is torch.float8_e4m3fn (quantized
 // with kv_descale: fp32 broadcastable to [B], or absent for 1.0). Returns new_seqlens int32 [B], a NEW tensor.
+// mixed (flash_attention_mla_append_mixed, include/fa_gfx950_mla_mixed.h fa_mla_append_mixed_gfx950): a torch.uint8
+// kv_cache [num_pages, page_size, 656] takes mixed rows, the per-tile scales computed on the device; bf16 rows.
 // Inputs the kernel's 16-byte loads cannot take are copied, the cache never. No host synchronisation.
-torch::Tensor flash_attention_mla_append(torch::Tensor &kv_cache, torch::Tensor &c_kv, torch::Tensor &k_pe,
-                                         torch::Tensor &cache_seqlens, torch::Tensor &block_table,
-                                         c10::optional<torch::Tensor> kv_descale) {
-    TORCH_CHECK(kv_cache.dim() == 3 && kv_cache.size(2) == 576, "kv_cache must be [pages, page_size, 576]");
+torch::Tensor mla_append_impl(torch::Tensor &kv_cache, torch::Tensor &c_kv, torch::Tensor &k_pe,
+                              torch::Tensor &cache_seqlens, torch::Tensor &block_table,
+                              c10::optional<torch::Tensor> kv_descale, const bool mixed) {
+    TORCH_CHECK(!mixed || kv_cache.dtype() == torch::kUInt8, "a mixed-row latent cache is torch.uint8");
+    TORCH_CHECK(kv_cache.dim() == 3 && kv_cache.size(2) == (mixed ? FA_MLA_MIXED_ROW_BYTES : 576),
+                "kv_cache must be [pages, page_size, 576], or [pages, page_size, 656] bytes of mixed rows");
     TORCH_CHECK(c_kv.dim() == 3 && c_kv.size(2) == 512 && k_pe.dim() == 3 && k_pe.size(2) == 64,
                 "c_kv must be [batch, new rows, 512] and k_pe [batch, new rows, 64]");
     TORCH_CHECK(c_kv.size(0) == k_pe.size(0) && c_kv.size(1) == k_pe.size(1), "c_kv and k_pe must agree in batch and rows");
     TORCH_CHECK(c_kv.dtype() == k_pe.dtype() && (c_kv.dtype() == torch::kHalf || c_kv.dtype() == torch::kBFloat16),
                 "c_kv and k_pe must both be fp16 or both bf16");
     const bool fp8 = kv_cache.dtype() == torch::kFloat8_e4m3fn;
-    TORCH_CHECK(fp8 || kv_cache.dtype() == c_kv.dtype(), "kv_cache must have the data type of c_kv or be float8_e4m3fn");
+    TORCH_CHECK(fp8 || mixed || kv_cache.dtype() == c_kv.dtype(),
+                "kv_cache must have the data type of c_kv, be float8_e4m3fn or hold mixed rows (uint8)");
+    TORCH_CHECK(!mixed || c_kv.dtype() == torch::kBFloat16, "c_kv and k_pe must be bf16 for a mixed-row latent cache");
     TORCH_CHECK(fp8 || !kv_descale.has_value(), "kv_descale goes with a float8_e4m3fn latent cache");
     TORCH_CHECK(kv_cache.size(0) > 0 && kv_cache.size(1) > 0, "kv_cache must have at least one page and one row");
     TORCH_CHECK(kv_cache.stride(2) == 1, "kv_cache must be contiguous in the last dimension");
@@ -1723,9 +1754,23 @@ torch::Tensor flash_attention_mla_append(torch::Tensor &kv_cache, torch::Tensor 
     p.max_pages = table.size(1);
     p.block_table_stride = table.stride(0);
     const int dtype = fa_dtype(ckv);
-    p.cache_dtype = fp8 ? FA_MLA_CACHE_E4M3 : dtype;
-    check_rc(fa_mla_append_gfx950(&p, dtype, current_stream(kv_cache)), "fa_mla_append_gfx950");
+    p.cache_dtype = mixed ? FA_MLA_CACHE_MIXED : fp8 ? FA_MLA_CACHE_E4M3 : dtype;
+    if (mixed)
+        check_rc(fa_mla_append_mixed_gfx950(&p, dtype, current_stream(kv_cache)), "fa_mla_append_mixed_gfx950");
+    else
+        check_rc(fa_mla_append_gfx950(&p, dtype, current_stream(kv_cache)), "fa_mla_append_gfx950");
     return new_seqlens;
+}
+
+torch::Tensor flash_attention_mla_append(torch::Tensor &kv_cache, torch::Tensor &c_kv, torch::Tensor &k_pe,
+                                         torch::Tensor &cache_seqlens, torch::Tensor &block_table,
+                                         c10::optional<torch::Tensor> kv_descale) {
+    return mla_append_impl(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale, false);
+}
+
+torch::Tensor flash_attention_mla_append_mixed(torch::Tensor &kv_cache, torch::Tensor &c_kv, torch::Tensor &k_pe,
+                                               torch::Tensor &cache_seqlens, torch::Tensor &block_table) {
+    return mla_append_impl(kv_cache, c_kv, k_pe, cache_seqlens, block_table, c10::nullopt, true);
 }
 
 }  // namespace flash_attention
@@ -1797,4 +1842,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_mla_sparse_decode_fwd", &flash_attention::flash_attention_mla_sparse_decode_fwd,
           "Sparse MLA decode over top-k token indices (int32 [B, Sq, topk]) of a paged latent KV cache, (out, lse), gfx950");
     m.def("mla_sparse_version", []() { return fa_mla_sparse_version(); });
+    m.def("flash_attention_mla_sparse_mixed_decode_fwd", &flash_attention::flash_attention_mla_sparse_mixed_decode_fwd,
+          "Sparse MLA decode over a paged cache of mixed FP8 rows (656 bytes: e4m3 + tile scales + bf16 RoPE), bf16 q, gfx950");
+    m.def("flash_attention_mla_append_mixed", &flash_attention::flash_attention_mla_append_mixed,
+          "Append latent rows to a paged cache of mixed FP8 rows (per-tile scales computed on the device), one HIP launch");
+    m.def("mla_mixed_version", []() { return fa_mla_mixed_version(); });
 }

@@ -2108,10 +2108,12 @@ def flash_attention_mla_decode_forward_fake(q, kv_cache, block_table, cache_seql
     return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
 
 
-def _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale, causal):
+def _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale, causal,
+                          widen=torch.Tensor.float):
     """The non-GPU default of ``mla_sparse_decode_forward``, a float restatement: per (b, pos) the entries with
     ``0 <= idx <= lim`` (``lim`` the dense call's: the clamped length - 1, with ``causal`` at most
-    ``pos + length - Sq``) are gathered through the table, duplicates as repeated rows; nothing else is read."""
+    ``pos + length - Sq``) are gathered through the table, duplicates as repeated rows; nothing else is read.
+    ``widen`` turns the gathered pool rows into their 576 float columns."""
     b_, hq, sq, _ = q.shape
     num_pages, page_size, _ = kv_cache.shape
     cap = block_table.size(1) * page_size
@@ -2126,7 +2128,7 @@ def _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, soft
             if idx.numel() == 0:
                 continue
             pages = block_table[b].index_select(0, idx // page_size).clamp(0, num_pages - 1).to(torch.int64)
-            kv = kv_cache[pages, idx % page_size].float()
+            kv = widen(kv_cache[pages, idx % page_size])
             s = torch.matmul(q[b, :, pos].float(), kv.t()) * softmax_scale  # [Hq, n_visible]
             l = torch.logsumexp(s, dim=-1)
             out[b, :, pos], lse[b, :, pos] = torch.matmul(torch.exp(s - l[:, None]), kv[:, :_MLA_DV]), l
@@ -2194,8 +2196,15 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
     for it and it contributes exactly nothing. The list is unsorted; a duplicate counts once per occurrence. A
     row without a visible entry gives ``out`` 0 and ``lse`` -inf; the lse merges with
     ``flash_attn_merge_states``, so a list sharded over devices is expressible. ``num_splits`` then splits a
-    list's ``topk / 32`` tiles. 16-bit cache only: with an FP8 cache or ``kv_descale`` it raises
-    ``NotImplementedError``. ``indices=None`` is the dense call."""
+    list's ``topk / 32`` tiles. With a 576-byte FP8 cache or ``kv_descale`` it raises ``NotImplementedError``.
+    ``indices=None`` is the dense call.
+
+    A ``torch.uint8`` ``kv_cache`` [num_pages, page_size, 656] (row stride a multiple of 16) holds DeepSeek-V3.2's
+    MIXED rows (FlashMLA's sparse-decode row, vLLM's ``fp8_ds_mla``): 512 e4m3 bytes, four fp32 scales (scale j
+    covers columns [128 j, 128 j + 128): value = e4m3 * scale[j]) and the 64 RoPE columns as bf16. It is read in
+    place by a sparse kernel of its own (``indices`` required, bf16 ``q``; no ``kv_descale``: the row carries its
+    scales): the result is that of the bf16 sparse call over the dequantised rows. ``flash_attn_mla_append``
+    writes such rows."""
     if softmax_scale is None:
         raise TypeError("flash_attn_mla_decode_func needs softmax_scale: there is no default for MLA "
                         "(the absorbed head dim 576 is not the model's scale dim)")
@@ -2206,16 +2215,19 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
                                   f"{tuple(q.shape)}, head_dim_v {head_dim_v})")
     if kv_cache.dim() == 4 and 1 in (kv_cache.size(1), kv_cache.size(2)):
         kv_cache = kv_cache.squeeze(1 if kv_cache.size(1) == 1 else 2)
-    if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
-        raise ValueError(f"kv_cache must be [num_pages, page_size, 576], or 4-D with a singleton head axis "
-                         f"(got {tuple(kv_cache.shape)})")
+    if kv_cache.dim() != 3 or kv_cache.size(-1) not in (_MLA_DQK, _MLA_MIXED_ROW):
+        raise ValueError(f"kv_cache must be [num_pages, page_size, 576] (656 bytes for mixed rows), or 4-D with a "
+                         f"singleton head axis (got {tuple(kv_cache.shape)})")
+    mixed = _is_mixed_latent(kv_cache, kv_descale, q)
+    if mixed and indices is None:
+        raise NotImplementedError("a mixed-row latent cache is read by the sparse decode (indices=) only")
     if indices is not None and (kv_descale is not None or kv_cache.dtype == FP8_DTYPE):
         raise NotImplementedError("sparse MLA decode (indices=) is built for a 16-bit latent cache only: "
                                   "no FP8 cache and no kv_descale")
-    fp8 = _is_fp8_latent(kv_cache, kv_descale)
+    fp8 = not mixed and _is_fp8_latent(kv_cache, kv_descale)
     if fp8 and q.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"q must be fp16 or bf16 over a torch.float8_e4m3fn latent cache (got {q.dtype})")
-    if not fp8 and kv_cache.dtype != q.dtype:
+    if not fp8 and not mixed and kv_cache.dtype != q.dtype:
         raise ValueError(f"q and kv_cache must have the same data type (got {q.dtype} and {kv_cache.dtype})")
     if kv_cache.size(1) % 32 != 0:
         raise ValueError(f"page_size must be a multiple of 32 (got {kv_cache.size(1)})")
@@ -2226,8 +2238,10 @@ def flash_attn_mla_decode_func(q, kv_cache, block_table, cache_seqlens, softmax_
                 or indices.size(2) == 0 or indices.size(2) % 32 != 0):
             raise ValueError(f"indices must be int32 [B, Sq, topk] = [{q.size(0)}, {q.size(2)}, a positive multiple "
                              f"of 32] (pad the list with -1; got {indices.dtype} {tuple(indices.shape)})")
-        o, lse = torch.ops.flash_attention.mla_sparse_decode_forward(
-            q, kv_cache, block_table, cache_seqlens, indices, float(softmax_scale), bool(causal), int(num_splits))
+        op = torch.ops.flash_attention.mla_sparse_decode_forward_mixed if mixed else \
+            torch.ops.flash_attention.mla_sparse_decode_forward
+        o, lse = op(q, kv_cache, block_table, cache_seqlens, indices, float(softmax_scale), bool(causal),
+                    int(num_splits))
     elif fp8:
         o, lse = torch.ops.flash_attention.mla_decode_forward_fp8(
             q, kv_cache, block_table, cache_seqlens, _latent_descale(kv_descale, q.size(0), q.device),
@@ -2364,16 +2378,26 @@ def flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_d
     their bits unchanged; a ``torch.float8_e4m3fn`` cache takes ``e4m3_rne(clamp(x / kv_descale[b], -448, 448))``
     (``kv_descale``: fp32 broadcastable to [B], a Python float, or None = 1.0). The cache is never copied.
 
+    A ``torch.uint8`` cache [num_pages, page_size, 656] (or 4-D with a singleton head axis; row stride a multiple
+    of 16) takes MIXED rows (see ``flash_attn_mla_decode_func``), bf16 ``c_kv`` / ``k_pe`` only and no
+    ``kv_descale``: per token and 128-column tile ``scale = max(amax / 448, FLT_MIN)`` (vLLM's rule),
+    ``e4m3_rne(clamp(x / scale, -448, 448))``, the four scales, then the bits of ``k_pe``.
+
     Returns ``new_seqlens = min(cache_seqlens + Sn, capacity)``, a NEW int32 [B]; ``cache_seqlens`` is not
     modified. No host synchronisation (graph-capturable)."""
-    if kv_cache.dim() != 3 or kv_cache.size(-1) != _MLA_DQK:
-        raise ValueError(f"kv_cache must be [num_pages, page_size, 576] (got {tuple(kv_cache.shape)})")
+    if kv_cache.dim() == 4 and kv_cache.size(-1) == _MLA_MIXED_ROW and 1 in (kv_cache.size(1), kv_cache.size(2)):
+        kv_cache = kv_cache.squeeze(1 if kv_cache.size(1) == 1 else 2)
+    if kv_cache.dim() != 3 or kv_cache.size(-1) not in (_MLA_DQK, _MLA_MIXED_ROW):
+        raise ValueError(f"kv_cache must be [num_pages, page_size, 576] (656 bytes for mixed rows; got "
+                         f"{tuple(kv_cache.shape)})")
     if (c_kv.dim() != 3 or k_pe.dim() != 3 or c_kv.size(-1) != _MLA_DV or k_pe.size(-1) != _MLA_DQK - _MLA_DV
             or c_kv.shape[:2] != k_pe.shape[:2]):
         raise ValueError(f"c_kv must be [B, Sn, 512] and k_pe [B, Sn, 64] (got {tuple(c_kv.shape)} and "
                          f"{tuple(k_pe.shape)})")
     if c_kv.dtype != k_pe.dtype or c_kv.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"c_kv and k_pe must both be fp16 or both bf16 (got {c_kv.dtype} and {k_pe.dtype})")
+    if _is_mixed_latent(kv_cache, kv_descale, c_kv):
+        return torch.ops.flash_attention.mla_append_mixed(kv_cache, c_kv, k_pe, cache_seqlens, block_table)
     if _is_fp8_latent(kv_cache, kv_descale):
         return torch.ops.flash_attention.mla_append_fp8(kv_cache, c_kv, k_pe, cache_seqlens, block_table,
                                                         _latent_descale(kv_descale, c_kv.size(0), kv_cache.device))
@@ -2390,9 +2414,12 @@ def flash_attn_mla_with_kvcache(q, kv_cache, c_kv, k_pe, cache_seqlens, block_ta
     Returns ``out``, followed by ``lse`` with ``return_lse`` and by ``new_seqlens`` with ``return_seqlens``;
     ``cache_seqlens`` is not modified (the caller copies ``new_seqlens`` into it). ``indices`` (int32
     [B, Sq, topk], see ``flash_attn_mla_decode_func``) makes the decode sparse; its entries refer to the cache
-    AFTER the append (positions of the new tokens included)."""
+    AFTER the append (positions of the new tokens included). A mixed-row cache (``torch.uint8``, 656 bytes a token)
+    is served with ``indices`` only."""
     if indices is not None and (kv_descale is not None or kv_cache.dtype == FP8_DTYPE):  # (before the cache is written)
         raise NotImplementedError("sparse MLA decode (indices=) is built for a 16-bit latent cache only")
+    if indices is None and kv_cache.size(-1) == _MLA_MIXED_ROW:
+        raise NotImplementedError("a mixed-row latent cache is read by the sparse decode (indices=) only")
     new_seqlens = flash_attn_mla_append(kv_cache, c_kv, k_pe, cache_seqlens, block_table, kv_descale)
     res = flash_attn_mla_decode_func(q, kv_cache, block_table, new_seqlens, softmax_scale, causal,
                                      return_lse=return_lse, num_splits=num_splits, kv_descale=kv_descale,
@@ -2400,3 +2427,106 @@ def flash_attn_mla_with_kvcache(q, kv_cache, c_kv, k_pe, cache_seqlens, block_ta
     if not return_seqlens:
         return res
     return (*res, new_seqlens) if return_lse else (res, new_seqlens)
+
+
+# ---------------------------------------------------------------------------------------------
+# The MIXED FP8 latent row of DeepSeek-V3.2 (include/fa_gfx950_mla_mixed.h; FlashMLA's sparse-decode row, vLLM's
+# ``fp8_ds_mla``): 656 bytes a token -- 512 e4m3 bytes, four fp32 scales (one per 128 columns), 64 bf16 RoPE
+# columns. ``flash_attn_mla_decode_func(indices=)`` and ``flash_attn_mla_append`` reach these ops through a
+# ``torch.uint8`` cache [num_pages, page_size, 656]: fa_mla_sparse_decode_mixed gathers the rows in place.
+# ---------------------------------------------------------------------------------------------
+_MLA_MIXED_ROW = 656
+_MLA_MIXED_SCALES, _MLA_MIXED_ROPE = 512, 528  # byte offsets within a row
+
+
+def _is_mixed_latent(kv_cache, kv_descale, x16) -> bool:
+    """Whether the latent cache holds mixed rows (by its row width); the wrappers' errors for such a cache. ``x16``:
+    the 16-bit operand (q, or the new rows), which must be bf16."""
+    if kv_cache.size(-1) != _MLA_MIXED_ROW:
+        return False
+    if kv_cache.dtype != torch.uint8:
+        raise ValueError(f"a latent cache of 656-byte mixed rows must be torch.uint8, not {kv_cache.dtype}")
+    if kv_descale is not None:
+        raise ValueError("kv_descale does not go with a mixed-row latent cache: the row carries its scales")
+    if x16.dtype != torch.bfloat16:
+        raise ValueError(f"q, c_kv and k_pe must be bf16 with a mixed-row latent cache (got {x16.dtype})")
+    return True
+
+
+def pack_mla_mixed_rows(c_kv: torch.Tensor, k_pe: torch.Tensor) -> torch.Tensor:
+    """The write formula of a mixed row: uint8 [..., 656] from c_kv [..., 512] and the already rotated k_pe
+    [..., 64] (bf16). Per 128-column tile ``scale = max(amax / 448, FLT_MIN)`` and ``quantize_e4m3(x, scale)``."""
+    x = c_kv.float().unflatten(-1, (4, 128))
+    scale = (x.abs().amax(-1) / FP8_MAX).clamp_min(torch.finfo(torch.float32).tiny)
+    b8 = quantize_e4m3(x, scale[..., None]).view(torch.uint8).flatten(-2)
+    return torch.cat([b8, scale.contiguous().view(torch.uint8),
+                      k_pe.to(torch.bfloat16).contiguous().view(torch.uint8)], dim=-1)
+
+
+def unpack_mla_mixed_rows(rows: torch.Tensor) -> torch.Tensor:
+    """The 576 fp32 columns of mixed rows (uint8 [..., 656]): e4m3 * scale per tile (exact in fp32), then RoPE."""
+    rows = rows.contiguous()
+    scale = rows[..., _MLA_MIXED_SCALES:_MLA_MIXED_ROPE].contiguous().view(torch.float32)
+    nope = rows[..., :_MLA_MIXED_SCALES].contiguous().view(FP8_DTYPE).float().unflatten(-1, (4, 128)) * scale[..., None]
+    rope = rows[..., _MLA_MIXED_ROPE:].contiguous().view(torch.bfloat16).float()
+    return torch.cat([nope.flatten(-2), rope], dim=-1)
+
+
+@torch.library.custom_op("flash_attention::mla_sparse_decode_forward_mixed", mutates_args=())
+def flash_attention_mla_sparse_decode_forward_mixed(q: torch.Tensor, kv_cache: torch.Tensor, block_table: torch.Tensor,
+                                                    cache_seqlens: torch.Tensor, indices: torch.Tensor,
+                                                    softmax_scale: float, causal: bool = True,
+                                                    num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    # q [B, Hq, Sq, 576], kv_cache uint8 [num_pages, page_size, 656], indices int32 [B, Sq, topk] -> (o, lse).
+    # Non-GPU default: mla_sparse_decode_forward's default over the dequantised rows it gathers
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _mla_sparse_reference(q, kv_cache, block_table, cache_seqlens, indices, softmax_scale, causal,
+                                 unpack_mla_mixed_rows)
+
+
+@torch.library.register_kernel("flash_attention::mla_sparse_decode_forward_mixed", "cuda")
+def flash_attention_mla_sparse_decode_forward_mixed_cuda(q: torch.Tensor, kv_cache: torch.Tensor,
+                                                         block_table: torch.Tensor, cache_seqlens: torch.Tensor,
+                                                         indices: torch.Tensor, softmax_scale: float,
+                                                         causal: bool = True,
+                                                         num_splits: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_mla_sparse_mixed_decode_fwd(
+        q if q.stride(-1) == 1 else q.contiguous(), kv_cache, block_table, cache_seqlens, indices, softmax_scale,
+        causal, num_splits)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::mla_sparse_decode_forward_mixed")
+def flash_attention_mla_sparse_decode_forward_mixed_fake(q, kv_cache, block_table, cache_seqlens, indices,
+                                                         softmax_scale, causal=True, num_splits=0):
+    return q.new_empty((*q.shape[:3], _MLA_DV)), q.new_empty(q.shape[:3], dtype=torch.float32)
+
+
+@torch.library.custom_op("flash_attention::mla_append_mixed", mutates_args=("kv_cache",))
+def flash_attention_mla_append_mixed(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                                     cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    # kv_cache uint8 [num_pages, page_size, 656], c_kv [B, Sn, 512], k_pe [B, Sn, 64] -> new_seqlens [B].
+    # Non-GPU default: the placement and drop rules of _mla_append_reference over packed rows
+    num_pages, page_size, _ = kv_cache.shape
+    cap = block_table.size(1) * page_size
+    b_, sn = c_kv.shape[:2]
+    lens = cache_seqlens.clamp(0, cap).to(torch.int64)
+    if b_ > 0 and sn > 0:
+        pos = lens[:, None] + torch.arange(sn, device=lens.device)[None]  # [B, Sn]
+        page = block_table.to(torch.int64).gather(1, pos.clamp(max=cap - 1) // page_size)
+        ok = (pos < cap) & (page >= 0) & (page < num_pages)
+        kv_cache[page[ok], (pos % page_size)[ok]] = pack_mla_mixed_rows(c_kv, k_pe)[ok]
+    return (lens + sn).clamp(max=cap).to(torch.int32)
+
+
+@torch.library.register_kernel("flash_attention::mla_append_mixed", "cuda")
+def flash_attention_mla_append_mixed_cuda(kv_cache: torch.Tensor, c_kv: torch.Tensor, k_pe: torch.Tensor,
+                                          cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    _require_ext()
+    return flash_attention_cuda.flash_attention_mla_append_mixed(kv_cache, c_kv, k_pe, cache_seqlens, block_table)
+
+
+@torch.library.register_fake("flash_attention::mla_append_mixed")
+def flash_attention_mla_append_mixed_fake(kv_cache, c_kv, k_pe, cache_seqlens, block_table):
+    return torch.empty_like(cache_seqlens)
