@@ -14,8 +14,9 @@ into the package directory so the artefacts travel with the repository snapshot.
      csrc/fa_paged_varlen_lse_gfx950.hip (C-ABI dispatchers) + csrc/fa_rope.hip,
      csrc/fa_kvcache.hip, csrc/fa_kvcache_fp8.hip, csrc/fa_kvcache_varlen.hip, csrc/fa_merge.hip,
      csrc/fa_mla_gfx950.hip, csrc/fa_mla_fp8_gfx950.hip, csrc/fa_mla_append.hip, csrc/fa_mla_sparse_gfx950.hip,
-     csrc/fa_mla_sparse_mixed_gfx950.hip, csrc/fa_mla_append_mixed.hip
-     (stand-alone kernels with their entries; the last six are the MLA decode over a paged latent cache, the same
+     csrc/fa_mla_sparse_mixed_gfx950.hip, csrc/fa_mla_append_mixed.hip, csrc/fa_mla_prefill_gfx950.hip
+     (stand-alone kernels with their entries; the last is the MLA prefill attention, 192-column keys and 128-column
+     values over packed sequences, both dtypes; the six before it are the MLA decode over a paged latent cache, the same
      over an FP8 (e4m3) latent cache, the latent cache's append, the sparse MLA decode over top-k token
      indices, both dtypes in each file, and the sparse decode and the append on DeepSeek-V3.2's mixed FP8 row, bf16;
      the four decodes share the host layer of csrc/fa_mla_host.h)
@@ -24,7 +25,8 @@ into the package directory so the artefacts travel with the repository snapshot.
      include/fa_gfx950_paged_prefill.h, include/fa_gfx950_lse.h, include/fa_gfx950_paged_varlen.h,
      include/fa_gfx950_kvcache_varlen.h, include/fa_gfx950_sink.h, include/fa_gfx950_paged_varlen_sink.h,
      include/fa_gfx950_paged_varlen_lse.h, include/fa_gfx950_mla.h, include/fa_gfx950_mla_fp8.h,
-     include/fa_gfx950_mla_sparse.h and include/fa_gfx950_mla_mixed.h; no torch symbols)
+     include/fa_gfx950_mla_sparse.h, include/fa_gfx950_mla_mixed.h and include/fa_gfx950_mla_prefill.h; no torch
+     symbols)
   2. ``g++``  csrc/flash_attention_api.cpp  ->  _C<ext>.so  (pybind11 torch binding, linked
      against lib/libfa_gfx950.so with an $ORIGIN rpath)
 
@@ -66,13 +68,14 @@ def _stale(out: Path, inputs: list[Path]) -> bool:
     return any(p.stat().st_mtime > t for p in inputs if p.exists())
 
 
-def _run(cmd: list[str], verbose: bool) -> None:
+def _run(cmd: list[str], verbose: bool) -> str:
     if verbose:
         print("+", " ".join(str(c) for c in cmd), flush=True)
     res = subprocess.run([str(c) for c in cmd], capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError(f"build step failed ({res.returncode}):\n{' '.join(map(str, cmd))}\n"
                            f"{res.stdout}\n{res.stderr}")
+    return res.stderr
 
 
 def abi_sources() -> list[Path]:
@@ -112,7 +115,12 @@ HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mcode-obj
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"fa_mla_gfx950.hip": _NO_PK_F32, "fa_mla_fp8_gfx950.hip": _NO_PK_F32, "fa_mla_append.hip": _NO_PK_F32,
                 "fa_mla_sparse_gfx950.hip": _NO_PK_F32, "fa_mla_sparse_mixed_gfx950.hip": _NO_PK_F32,
-                "fa_mla_append_mixed.hip": _NO_PK_F32}
+                "fa_mla_append_mixed.hip": _NO_PK_F32,
+                # (the prefill kernel: MFMA results in VGPRs, where its online-softmax rescale reads them -- with the
+                # accumulators in AGPRs the key loop copied all 128 of them both ways every tile; and the resource
+                # remarks, which compile_one reads: no kernel of it may use scratch)
+                "fa_mla_prefill_gfx950.hip": _NO_PK_F32 + ["-mllvm", "-amdgpu-mfma-vgpr-form=1",
+                                                           "-Rpass-analysis=kernel-resource-usage"]}
 
 
 def _jobs() -> int:
@@ -196,13 +204,13 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
     # with sinks, ragged paged prefill with sinks, ragged paged prefill with the LSE), standalone RoPE kernel, KV-cache append kernels (uniform, FP8, ragged), merge_states kernel,
     # MLA decode (checks, kernel selection and entries; the kernels are fa_mla_decode.hpp's, the plan, workspace and
     # launch fa_mla_host.h's), the same over an FP8 latent cache, the latent append, the sparse MLA decode over top-k
-    # token indices, the sparse decode and the append on the mixed FP8 row
+    # token indices, the sparse decode and the append on the mixed FP8 row, the MLA prefill attention
     for src in ("fa_fwd_gfx950.hip", "fa_paged_gfx950.hip", "fa_paged_prefill_gfx950.hip", "fa_paged_lse_gfx950.hip",
                 "fa_paged_varlen_gfx950.hip", "fa_paged_sink_gfx950.hip", "fa_paged_varlen_sink_gfx950.hip",
                 "fa_paged_varlen_lse_gfx950.hip", "fa_rope.hip", "fa_kvcache.hip", "fa_kvcache_fp8.hip",
                 "fa_kvcache_varlen.hip", "fa_merge.hip", "fa_mla_gfx950.hip", "fa_mla_fp8_gfx950.hip",
                 "fa_mla_append.hip", "fa_mla_sparse_gfx950.hip", "fa_mla_sparse_mixed_gfx950.hip",
-                "fa_mla_append_mixed.hip"):
+                "fa_mla_append_mixed.hip", "fa_mla_prefill_gfx950.hip"):
         obj = objdir / src.replace(".hip", ".o")
         objs.append(obj)
         cmds.append(([HIPCC, *HIP_FLAGS, *SOURCE_FLAGS.get(src, []), *extra, f"-I{INCLUDE}", f"-I{CSRC}", "-c", CSRC / src,
@@ -216,7 +224,12 @@ def build_abi(force: bool = False, verbose: bool = False, stamps: bool = False, 
                 and (obj.name not in [f"{name}.o" for _, name in INST_TUS]
                      or next(obj.parent.glob("*.s"), None) is not None)):
             return
-        _run(cmd, verbose)
+        remarks = _run(cmd, verbose)
+        # a source compiled with the resource-usage remarks (SOURCE_FLAGS) may not use scratch in any kernel
+        spilled = [ln for ln in remarks.splitlines()
+                   if "ScratchSize [bytes/lane]:" in ln and "ScratchSize [bytes/lane]: 0 " not in ln + " "]
+        if spilled:
+            raise RuntimeError(f"{obj.name}: a kernel uses scratch memory:\n" + "\n".join(spilled[:8]))
         stamp.write_text(line)
 
     with ThreadPoolExecutor(max_workers=_jobs()) as ex:

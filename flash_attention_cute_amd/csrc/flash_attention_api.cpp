@@ -36,6 +36,7 @@
 #include "fa_gfx950_mla.h"
 #include "fa_gfx950_mla_fp8.h"
 #include "fa_gfx950_mla_mixed.h"
+#include "fa_gfx950_mla_prefill.h"
 #include "fa_gfx950_mla_sparse.h"
 #include "fa_gfx950_paged.h"
 #include "fa_gfx950_paged_prefill.h"
@@ -1773,6 +1774,93 @@ torch::Tensor flash_attention_mla_append_mixed(torch::Tensor &kv_cache, torch::T
     return mla_append_impl(kv_cache, c_kv, k_pe, cache_seqlens, block_table, c10::nullopt, true);
 }
 
+// MLA prefill attention over packed sequences (include/fa_gfx950_mla_prefill.h fa_mla_prefill_gfx950): q [total_q, Hq,
+// 192], v [total_k, Hkv, 128], and the key either as k [total_k, Hkv, 192] or, with k_pe, as k [total_k, Hkv, 128]
+// (the nope columns) and k_pe [total_k, 1 or Hkv, 64] (the RoPE columns; a singleton head axis is one stream shared by
+// every head: head stride 0). Returns (out [total_q, Hq, 128], lse fp32 [Hq, total_q]). Strided views are taken in
+// place where the kernel's 16-byte loads can (v as half of a kv_b_proj output, q transposed); anything else is
+// copied. No host synchronisation.
+std::tuple<torch::Tensor, torch::Tensor> flash_attention_mla_prefill_fwd(
+    torch::Tensor &q, torch::Tensor &k, torch::Tensor &v, torch::Tensor &cu_seqlens_q, torch::Tensor &cu_seqlens_k,
+    int64_t max_seqlen_q, float softmax_scale, bool causal, c10::optional<torch::Tensor> k_pe) {
+    const bool split = k_pe.has_value();
+    TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3 && (!split || k_pe->dim() == 3),
+                "q, k, v (and k_pe) must be 3-D [total rows, heads, columns]");
+    TORCH_CHECK(q.size(2) == 192 && v.size(2) == 128 && k.size(2) == (split ? 128 : 192) && (!split || k_pe->size(2) == 64),
+                "MLA prefill is built for 192 query / key columns (128 + 64 with k_pe) and 128 value columns only");
+    TORCH_CHECK(q.dtype() == torch::kHalf || q.dtype() == torch::kBFloat16, "q, k, v only support fp16 or bf16 data type");
+    TORCH_CHECK(k.dtype() == q.dtype() && v.dtype() == q.dtype() && (!split || k_pe->dtype() == q.dtype()),
+                "q, k, v (and k_pe) must have the same data type");
+    const int64_t total_q = q.size(0), total_k = k.size(0), hq = q.size(1), hkv = k.size(1);
+    TORCH_CHECK(hq > 0 && hkv > 0 && hq % hkv == 0 && v.size(1) == hkv && v.size(0) == total_k,
+                "k and v must agree in rows and heads, and the q heads be a multiple of theirs");
+    TORCH_CHECK(!split || (k_pe->size(0) == total_k && (k_pe->size(1) == 1 || k_pe->size(1) == hkv)),
+                "k_pe must be [total_k, 1 or Hkv, 64]");
+    TORCH_CHECK(q.is_cuda() && k.device() == q.device() && v.device() == q.device() &&
+                    (!split || k_pe->device() == q.device()),
+                "q, k, v (and k_pe) must be on the same CUDA device");
+    auto check_cu = [&](const torch::Tensor &cu, const char *name) {
+        TORCH_CHECK(cu.dtype() == torch::kInt32 && cu.dim() == 1 && cu.size(0) >= 1 && cu.device() == q.device(), name,
+                    " must be int32 [batch + 1] on the device of q");
+    };
+    check_cu(cu_seqlens_q, "cu_seqlens_q");
+    check_cu(cu_seqlens_k, "cu_seqlens_k");
+    TORCH_CHECK(cu_seqlens_q.size(0) == cu_seqlens_k.size(0), "cu_seqlens_q and cu_seqlens_k must have the same length");
+    TORCH_CHECK(max_seqlen_q >= 0, "max_seqlen_q must be non-negative");
+    c10::DeviceGuard device_guard(q.device());
+    require_gfx950(q.device());
+
+    auto rows16 = [](const torch::Tensor &t) {  // [rows, heads, columns] the kernel reads in place, or a copy
+        const bool ok = t.stride(2) == 1 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                        t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(0) >= t.size(2) && t.stride(1) >= 0;
+        return ok ? t : t.contiguous();
+    };
+    torch::Tensor qx = rows16(q), kx = rows16(k), vx = rows16(v), px = split ? rows16(*k_pe) : kx;
+    torch::Tensor cq = cu_seqlens_q.contiguous(), ck = cu_seqlens_k.contiguous();
+    torch::Tensor o = torch::empty({total_q, hq, 128}, q.options());
+    torch::Tensor lse = torch::empty({hq, total_q}, q.options().dtype(torch::kFloat32));
+
+    fa_mla_prefill_params p;
+    memset(&p, 0, sizeof(p));
+    p.q_ptr = qx.data_ptr();
+    p.k_nope_ptr = kx.data_ptr();
+    p.k_rope_ptr = split ? px.data_ptr() : static_cast<void *>(static_cast<char *>(kx.data_ptr()) + 128 * 2);
+    p.v_ptr = vx.data_ptr();
+    p.o_ptr = o.data_ptr();
+    p.lse_ptr = lse.data_ptr<float>();
+    p.cu_seqlens_q = cq.data_ptr<int32_t>();
+    p.cu_seqlens_k = ck.data_ptr<int32_t>();
+    p.batch_size = cq.size(0) - 1;
+    p.total_q = total_q;
+    p.total_k = total_k;
+    p.max_seqlen_q = max_seqlen_q;
+    p.num_heads_q = hq;
+    p.num_heads_kv = hkv;
+    p.headdim_qk = 192;
+    p.headdim_v = 128;
+    p.q_row_stride = qx.stride(0);
+    p.q_head_stride = stride_or_zero(qx, 1);
+    p.k_nope_row_stride = kx.stride(0);
+    p.k_nope_head_stride = stride_or_zero(kx, 1);
+    p.k_rope_row_stride = px.stride(0);
+    p.k_rope_head_stride = stride_or_zero(px, 1);
+    p.v_row_stride = vx.stride(0);
+    p.v_head_stride = stride_or_zero(vx, 1);
+    p.o_row_stride = o.stride(0);
+    p.o_head_stride = o.stride(1);
+    p.lse_head_stride = lse.stride(0);
+    p.lse_row_stride = lse.stride(1);
+    softmax_scale *= M_LOG2E;  // (as fill_params)
+    p.softmax_scale = softmax_scale;
+    p.causal = causal ? 1 : 0;
+    if (total_k == 0) {  // (no key at all: every row is the row without a visible key)
+        o.zero_();
+        lse.fill_(-std::numeric_limits<float>::infinity());
+    } else if (total_q > 0)
+        check_rc(fa_mla_prefill_gfx950(&p, fa_dtype(qx), current_stream(qx)), "fa_mla_prefill_gfx950");
+    return std::make_tuple(o, lse);
+}
+
 }  // namespace flash_attention
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1847,4 +1935,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("flash_attention_mla_append_mixed", &flash_attention::flash_attention_mla_append_mixed,
           "Append latent rows to a paged cache of mixed FP8 rows (per-tile scales computed on the device), one HIP launch");
     m.def("mla_mixed_version", []() { return fa_mla_mixed_version(); });
+    m.def("flash_attention_mla_prefill_fwd", &flash_attention::flash_attention_mla_prefill_fwd,
+          "MLA prefill attention over packed sequences (192 key / 128 value columns, optional split key), (out, lse), gfx950");
+    m.def("mla_prefill_version", []() { return fa_mla_prefill_version(); });
 }

@@ -2530,3 +2530,128 @@ def flash_attention_mla_append_mixed_cuda(kv_cache: torch.Tensor, c_kv: torch.Te
 @torch.library.register_fake("flash_attention::mla_append_mixed")
 def flash_attention_mla_append_mixed_fake(kv_cache, c_kv, k_pe, cache_seqlens, block_table):
     return torch.empty_like(cache_seqlens)
+
+
+# ---------------------------------------------------------------------------------------------
+# MLA prefill attention over packed sequences (include/fa_gfx950_mla_prefill.h). No reference counterpart; the
+# prompt pass of DeepSeek-V2 / V3 / R1 and Kimi-K2 in the NON-absorbed form: per head 192 query / key columns
+# (128 "nope", then 64 RoPE) and 128 value columns, multi-head, packed, bottom-right causal or not.
+# ---------------------------------------------------------------------------------------------
+_MLA_PREFILL_DQK, _MLA_PREFILL_DV, _MLA_PREFILL_NOPE = 192, 128, 128
+
+
+def _mla_prefill_reference(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, softmax_scale, causal, k_pe):
+    """The non-GPU default of ``mla_prefill_forward``, a float restatement: (out, lse) with the kernel's semantics
+    (both cu arrays clamped to [0, total] and to non-decreasing, bottom-right causal per sequence, rows without a
+    visible key out = 0 and lse = -inf; rows past the blocks ``max_seqlen_q`` gives are left 0 / -inf)."""
+    total_q, hq, _ = q.shape
+    total_k, hkv, _ = k.shape
+    if k_pe is not None:
+        k = torch.cat([k, k_pe.expand(total_k, hkv, k_pe.size(-1))], dim=-1)
+    out = torch.zeros((total_q, hq, _MLA_PREFILL_DV), dtype=torch.float32, device=q.device)
+    lse = torch.full((hq, total_q), float("-inf"), dtype=torch.float32, device=q.device)
+    block = 128 if max_seqlen_q <= 128 else 256
+    cover = -(-max_seqlen_q // block) * block
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    for b in range(len(cq) - 1):
+        q0, k0 = min(max(cq[b], 0), total_q), min(max(ck[b], 0), total_k)
+        sq, sk = min(max(cq[b + 1], q0), total_q) - q0, min(max(ck[b + 1], k0), total_k) - k0
+        rows = min(sq, cover)
+        if rows == 0 or sk == 0:
+            continue
+        kb = k[k0:k0 + sk].float().repeat_interleave(hq // hkv, dim=1)
+        vb = v[k0:k0 + sk].float().repeat_interleave(hq // hkv, dim=1)
+        s = torch.einsum("mhd,nhd->hmn", q[q0:q0 + rows].float(), kb) * softmax_scale
+        if causal:
+            s = s.masked_fill(~_bottom_right_causal(sq, sk, q.device)[None, :rows], float("-inf"))
+        l = torch.logsumexp(s, dim=-1)
+        p = torch.exp(s - l.masked_fill(l == float("-inf"), 0)[..., None])
+        out[q0:q0 + rows] = torch.einsum("hmn,nhd->mhd", p, vb)
+        lse[:, q0:q0 + rows] = l
+    return out.to(q.dtype), lse
+
+
+@torch.library.custom_op("flash_attention::mla_prefill_forward", mutates_args=())
+def flash_attention_mla_prefill_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                                        cu_seqlens_k: torch.Tensor, max_seqlen_q: int, softmax_scale: float,
+                                        causal: bool = True,
+                                        k_pe: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    # q [total_q, Hq, 192], k [total_k, Hkv, 192] (or [.., 128] with k_pe [total_k, 1 or Hkv, 64]), v [total_k, Hkv, 128]
+    # -> (out [total_q, Hq, 128], lse fp32 [Hq, total_q])
+    warnings.warn("Flash Attention only support cuda now, fallback to pytorch implementation.", stacklevel=2)
+    return _mla_prefill_reference(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, softmax_scale, causal, k_pe)
+
+
+@torch.library.register_kernel("flash_attention::mla_prefill_forward", "cuda")
+def flash_attention_mla_prefill_forward_cuda(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                             cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
+                                             softmax_scale: float, causal: bool = True,
+                                             k_pe: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    _require_ext()
+    o, lse = flash_attention_cuda.flash_attention_mla_prefill_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                                                  softmax_scale, causal, k_pe)
+    return o, lse
+
+
+@torch.library.register_fake("flash_attention::mla_prefill_forward")
+def flash_attention_mla_prefill_forward_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, softmax_scale,
+                                             causal=True, k_pe=None):
+    return (q.new_empty((q.size(0), q.size(1), _MLA_PREFILL_DV)),
+            q.new_empty((q.size(1), q.size(0)), dtype=torch.float32))
+
+
+def flash_attn_mla_prefill_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale,
+                                causal=True, return_lse=False, k_pe=None):
+    """MLA prefill attention over packed sequences, one HIP kernel: the NON-absorbed form of DeepSeek-V2 / V3 / R1
+    and Kimi-K2, ``out[t, h] = softmax_n(softmax_scale q[t, h, :192] . k[n, h / g, :192]) v[n, h / g, :128]``.
+
+    ``q`` [total_q, Hq, 192], ``k`` [total_k, Hkv, 192], ``v`` [total_k, Hkv, 128] (fp16 or bf16, one dtype,
+    ``Hq % Hkv == 0``), ``cu_seqlens_q`` / ``cu_seqlens_k`` int32 [B + 1] on the device (clamped there to [0, total]
+    and to non-decreasing). Sequence b's queries are its LAST ``Sq_b`` positions: with ``causal``, key n is visible
+    to query m iff ``n <= m + Sk_b - Sq_b``; ``Sq_b != Sk_b`` is allowed either way, and ``causal=False`` is the pass
+    of a chunked prompt over the context already cached. ``max_seqlen_q`` sizes the grid (the contract of
+    ``flash_attn_varlen_func``: a smaller value leaves rows uncomputed); ``max_seqlen_k`` is accepted for symmetry
+    and not read. ``softmax_scale`` is required (with YaRN it is not ``192 ** -0.5``).
+
+    SPLIT KEY: with ``k_pe`` [total_k, 1 or Hkv, 64], ``k`` is [total_k, Hkv, 128], the "nope" columns, and ``k_pe``
+    the RoPE columns -- with a singleton head axis ONE stream shared by every head, read in place: no
+    ``torch.cat([k_nope, k_pe.expand(...)])`` copy. The result is bit-equal to the concatenated call. Strided views
+    whose rows the kernel's 16-byte loads can take are read in place too (``v`` as the ``[..., 128:]`` half of a
+    ``kv_b_proj`` output, ``q`` transposed); anything else is copied.
+
+    Returns ``out`` [total_q, Hq, 128] in q's dtype (a row without a visible key is 0), with ``return_lse`` also the
+    fp32 log-sum-exp [Hq, total_q] (natural log, ``-inf`` for such a row): the packed states
+    ``flash_attn_merge_states`` takes, so the causal pass over a new chunk and the non-causal pass over the cached
+    context merge as they are. No host synchronisation (graph-capturable)."""
+    if softmax_scale is None:
+        raise TypeError("flash_attn_mla_prefill_func needs softmax_scale: there is no default for MLA "
+                        "(with YaRN it is not 192 ** -0.5)")
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise RuntimeError(f"softmax_scale must be finite and > 0 (got {softmax_scale})")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or (k_pe is not None and k_pe.dim() != 3):
+        raise ValueError(f"q, k, v (and k_pe) must be 3-D [total rows, heads, columns] (got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)})")
+    k_width = k.size(-1) + (k_pe.size(-1) if k_pe is not None else 0)
+    if q.size(-1) != k_width:
+        raise ValueError(f"q and k (with k_pe) must have the same number of columns (got {q.size(-1)} and {k_width})")
+    if (q.size(-1), v.size(-1)) != (_MLA_PREFILL_DQK, _MLA_PREFILL_DV) or \
+            (k_pe is not None and k.size(-1) != _MLA_PREFILL_NOPE):
+        raise NotImplementedError(f"MLA prefill is built for head dims (192, 128) only, 128 + 64 with k_pe (got q "
+                                  f"{tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)})")
+    # (the float default of the op off the GPU takes any one dtype; the kernel the two 16-bit ones)
+    if (q.is_cuda and q.dtype not in (torch.float16, torch.bfloat16)) or k.dtype != q.dtype or v.dtype != q.dtype or \
+            (k_pe is not None and k_pe.dtype != q.dtype):
+        raise ValueError(f"q, k, v (and k_pe) must share one dtype, fp16 or bf16 (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if k.size(1) == 0 or q.size(1) % k.size(1) != 0 or v.shape[:2] != k.shape[:2]:
+        raise ValueError(f"k and v must agree in rows and heads and Hq be a multiple of Hkv (got q {tuple(q.shape)}, "
+                         f"k {tuple(k.shape)}, v {tuple(v.shape)})")
+    if k_pe is not None and (k_pe.size(0) != k.size(0) or k_pe.size(1) not in (1, k.size(1))):
+        raise ValueError(f"k_pe must be [total_k, 1 or Hkv, 64] (got {tuple(k_pe.shape)})")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() != cu_seqlens_q.numel() or cu.numel() < 1:
+            raise ValueError(f"{name} must be int32 [B + 1] (got {cu.dtype} {tuple(cu.shape)})")
+    if max_seqlen_q < 0:
+        raise ValueError(f"max_seqlen_q must be non-negative (got {max_seqlen_q})")
+    o, lse = torch.ops.flash_attention.mla_prefill_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                                                           float(softmax_scale), bool(causal), k_pe)
+    return (o, lse) if return_lse else o
